@@ -1,6 +1,8 @@
 """Throughput benchmark of the north-star hot path: LIDARLocRooms-v0 vectorized step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]              # 1 GPU
+    python bench.py --full ...                                 # + kernel-time pass, roofline, episode, CPU baseline
+    python bench.py --dump-outputs DIR ...                     # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N [--steps K] [--warmup W]          # N GPUs: bench.py starts the N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W        # the same under torchrun
@@ -13,7 +15,9 @@ steps include the map-generation reset bursts at the reference's 1-in-101 rate).
 scaling, each rank owns an independent env shard (seed offset rank*N), no data-path collective
 (--gather adds the optional RCCL all-gather of the step outputs and reports its time separately).
 
-Prints ONE JSON line on rank 0 (value = env-steps/s summed over all GPUs).
+Prints ONE JSON line on rank 0 (value = env-steps/s summed over all GPUs).  A plain run sets up, warms up, times
+the K steps and prints the line; `--full` adds everything that takes runs of its own: the kernel-time pass behind
+`roofline` and `config.gather_ms`, the one-episode measurement (`episode`) and the CPU baseline (`cpu_baseline`).
 
 `--workload mnist` / `--workload tinyimagenet-loc` measure the image glimpse path on BASELINE.json
 configs 4 and 5 instead (synthetic uint8 pools of the datasets' shapes; same JSON contract, the
@@ -110,6 +114,60 @@ def cpu_baseline(beams: int, size: int, kind: str, num_envs: int | None, steps: 
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(out_dir: str, result) -> None:
+    """--dump-outputs: what the last timed step returned, (obs, reward, terminated, truncated, info), as
+    <out_dir>/<name>.npy (name = the keys joined by dots).  Integers of 32 bits and more and float64 are written as
+    float64, everything else as float32.  Entries a `_key` mask of the vector-env info convention marks as not set are
+    written as 0.  When everything together would pass the budget, every array keeps the same fixed fraction of its
+    rows: a default_rng(0) sample of its leading dimension, so arrays over the same envs keep the same envs."""
+    import torch
+
+    leaves = []  # (name, array, mask or None)
+
+    def walk(name, v, mask):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                m = v.get("_" + k) if isinstance(k, str) and not k.startswith("_") else None
+                walk(f"{name}.{k}" if name else str(k), x, m if m is not None and not isinstance(m, dict) else mask)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}", x, mask)
+        elif isinstance(v, torch.Tensor) or (isinstance(v, np.ndarray) and v.dtype != object):
+            leaves.append((name, v, mask))
+
+    for name, v in zip(("obs", "reward", "terminated", "truncated", "info"), result):
+        walk(name, v, None)
+
+    def wide(v):
+        dt = str(v.dtype).replace("torch.", "")
+        return dt in ("float64", "int32", "uint32", "int64", "uint64")
+
+    total = sum(int(np.prod(v.shape)) * (8 if wide(v) else 4) for _, v, _ in leaves)
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v, mask in leaves:
+        rows = None
+        if frac < 1.0 and v.ndim >= 1 and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))
+
+        def host(x):
+            if isinstance(x, torch.Tensor):
+                if rows is not None:
+                    x = x[torch.as_tensor(rows, device=x.device)]
+                return x.detach().cpu().numpy()
+            return x[rows] if rows is not None else x
+
+        usable = mask is not None and v.ndim >= 1 and tuple(mask.shape) == (v.shape[0],)
+        a = host(v).astype(np.float64 if wide(v) else np.float32)
+        if usable:
+            a[~host(mask).astype(bool)] = 0
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # image workloads (BASELINE.json configs 4, 5): per-GPU envs, pool, classes, sensor, kind
 IMAGE_WORKLOADS = {
     "mnist": dict(name="MNIST-v0 ImageClassificationVectorEnv", kind="cls", envs=65536, shape=(28, 28),
@@ -149,6 +207,38 @@ def image_cpu_baseline(w: dict, pool: np.ndarray, labels: np.ndarray, c: int, nu
                       f"after reset(seed=0) (reset untimed) incl. one autoreset ({dt:.1f} s)"}
 
 
+def image_roofline(args, w: dict, c: int, n_local: int, log_stats: bool, step_ms: float, launches_timed: int) -> dict:
+    """--full: the roofline block of an image workload from the kernel-time pass's mean event time `step_ms`."""
+    bpe = image_bytes_per_env_step(w["kind"], w["classes"], w["sensor"], c)
+    shape = {"num_envs": n_local, "sensor": list(w["sensor"]), "classes": w["classes"], "log_stats": log_stats}
+    # the step kernel's time: the rocprof duration table of these sources at this shape when there is one
+    # (the events around a launch the GPU is not backed up behind include the host's launch latency, and
+    # then exceed the wall time per step), else the events
+    dj, dpath = newest_table("durations", args.workload, "image", shape, lambda t: "step" in t.get("per_class", {}))
+    events_ms = step_ms
+    if dj is not None:
+        step_ms = dj["per_class"]["step"]["median_us"] / 1e3
+    achieved = bpe * (n_local // args.sub_batches) / (step_ms * 1e-3) / 1e9  # (the timed launch: sub-batch 0's)
+    tj, tpath = pmc_table(args.workload, "image", shape)
+    traffic = issue = traffic_cal = None
+    if tj is not None:
+        traffic = tj["hbm_bytes_per_launch"]["step"]
+        issue = issue_fractions(tj["per_launch"]["step"], step_ms)
+        issue["source"] = tpath
+        # u8 tap rows: dword gathers in 64-B runs; f32 glimpse / output stores
+        traffic_cal = calibrated_traffic(tj["per_launch"]["step"], "k_seg64_4", "k_store4")
+    bound, basis = derive_bound(achieved / HBM_PEAK_GBS, issue)
+    return {"bound": bound, "bound_basis": basis, "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_calibrated": traffic_cal, "traffic_source": tpath,
+            "kernel": "k_image_step_fused" if dj else "image step (all kernels, HIP events around the "
+                                                      "step's launches)",
+            "kernel_ms": step_ms, "kernel_ms_source": dpath or "hip events",
+            "kernel_ms_events": events_ms,
+            "launches_timed": launches_timed, "event_every": args.event_every,
+            "bytes_per_launch": bpe * (n_local // args.sub_batches), "issue": issue}
+
+
 def run_image(args, world, rank, dev):
     import torch
     import torch.distributed as dist
@@ -170,7 +260,8 @@ def run_image(args, world, rank, dev):
     senv = ShardedVectorEnv(lambda num_envs, env_offset, **kw: cls(num_envs, cfg, device=dev, array_backend="torch",
                                                                    num_envs_total=n_total, env_offset=env_offset,
                                                                    log_stats=log_stats, **kw),
-                            n_total, rank, world, gather=args.gather, time_gather=True, sub_batches=args.sub_batches)
+                            n_total, rank, world, gather=args.gather, time_gather=args.full,
+                            sub_batches=args.sub_batches)
     env = senv.env
     ring = 17
     g = torch.Generator(device=dev).manual_seed(1 + rank)
@@ -188,63 +279,49 @@ def run_image(args, world, rank, dev):
     for t in range(args.warmup):
         senv.step(inputs[t % ring])
     senv.gather_ms()
-    ev = HipEvents(args.steps)
     stepper = senv.step if senv.gather else env.step
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     # the timed window (`value`): K plain steps, no hipEvents between the launches (nor around the all-gathers)
     senv.time_gather = False
+    last = None
     t0 = time.perf_counter()
     for t in range(args.steps):
-        stepper(inputs[(args.warmup + t) % ring])
+        last = stepper(inputs[(args.warmup + t) % ring])
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     senv.check_errors()
-    # the kernel-time pass (roofline and gather_ms, not `value`): K more steps, hipEvents right around the step's
-    # kernel launches (inside env.step) on every event_every-th, and around every all-gather
-    senv.time_gather = True
-    timed = [t for t in range(args.steps) if t % args.event_every == args.event_every - 1]  # steps with hipEvents
-    for t in range(args.steps):
-        if t % args.event_every == args.event_every - 1:
-            env.set_kernel_timing_events(*ev.pair(t))
-            stepper(inputs[(args.warmup + args.steps + t) % ring])
-            env.set_kernel_timing_events(None)
-        else:
-            stepper(inputs[(args.warmup + args.steps + t) % ring])
-    env.set_kernel_timing_events(None)
-    torch.cuda.synchronize(dev)
-    senv.check_errors()
-    step_ms = sum(ev.elapsed_ms(i) for i in timed) / len(timed)
-    gather_ms = senv.gather_ms() or 0.0
-    ev.close()
+    if args.dump_outputs and rank == 0 and last is not None:  # (before later steps rewrite the output buffers)
+        dump_outputs(args.dump_outputs, last)
+    step_ms = gather_ms = 0.0
+    if args.full:
+        # the kernel-time pass (roofline and gather_ms, not `value`): K more steps, hipEvents right around the step's
+        # kernel launches (inside env.step) on every event_every-th, and around every all-gather
+        ev = HipEvents(args.steps)
+        senv.time_gather = True
+        timed = [t for t in range(args.steps) if t % args.event_every == args.event_every - 1]  # steps with hipEvents
+        for t in range(args.steps):
+            if t % args.event_every == args.event_every - 1:
+                env.set_kernel_timing_events(*ev.pair(t))
+                stepper(inputs[(args.warmup + args.steps + t) % ring])
+                env.set_kernel_timing_events(None)
+            else:
+                stepper(inputs[(args.warmup + args.steps + t) % ring])
+        env.set_kernel_timing_events(None)
+        torch.cuda.synchronize(dev)
+        senv.check_errors()
+        step_ms = sum(ev.elapsed_ms(i) for i in timed) / len(timed)
+        gather_ms = senv.gather_ms() or 0.0
+        ev.close()
     if world > 1:
         tt = torch.tensor([elapsed, step_ms, reset_ms, gather_ms], dtype=torch.float64,
                           device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, step_ms, reset_ms, gather_ms = (float(x) for x in tt)
     if rank == 0:
-        bpe = image_bytes_per_env_step(w["kind"], w["classes"], w["sensor"], c)
-        shape = {"num_envs": n_local, "sensor": list(w["sensor"]), "classes": w["classes"], "log_stats": log_stats}
-        # the step kernel's time: the rocprof duration table of these sources at this shape when there is one
-        # (the events around a launch the GPU is not backed up behind include the host's launch latency, and
-        # then exceed the wall time per step), else the events
-        dj, dpath = newest_table("durations", args.workload, "image", shape, lambda t: "step" in t.get("per_class", {}))
-        events_ms = step_ms
-        if dj is not None:
-            step_ms = dj["per_class"]["step"]["median_us"] / 1e3
-        achieved = bpe * (n_local // args.sub_batches) / (step_ms * 1e-3) / 1e9  # (the timed launch: sub-batch 0's)
-        tj, tpath = pmc_table(args.workload, "image", shape)
-        traffic = issue = traffic_cal = None
-        if tj is not None:
-            traffic = tj["hbm_bytes_per_launch"]["step"]
-            issue = issue_fractions(tj["per_launch"]["step"], step_ms)
-            issue["source"] = tpath
-            # u8 tap rows: dword gathers in 64-B runs; f32 glimpse / output stores
-            traffic_cal = calibrated_traffic(tj["per_launch"]["step"], "k_seg64_4", "k_store4")
-        bound, basis = derive_bound(achieved / HBM_PEAK_GBS, issue)
         out = {
             "metric": "env-steps/sec (vectorized step) at 1/2/4/8 MI355X + achieved HBM GB/s",
             "value": n_total * args.steps / elapsed, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
@@ -258,21 +335,14 @@ def run_image(args, world, rank, dev):
                        "reset_ms": reset_ms, "parallelism": f"env-shard x{world}" + (" + all-gather" if senv.gather
                                                                                         else ""),
                        "packed_rows": bool(senv._packed),
-                       "gather_ms": gather_ms if senv.gather else None},
-            "roofline": {"bound": bound, "bound_basis": basis, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_calibrated": traffic_cal, "traffic_source": tpath,
-                         "kernel": "k_image_step_fused" if dj else "image step (all kernels, HIP events around the "
-                                                                   "step's launches)",
-                         "kernel_ms": step_ms, "kernel_ms_source": dpath or "hip events",
-                         "kernel_ms_events": events_ms,
-                         "launches_timed": len(timed), "event_every": args.event_every,
-                         "bytes_per_launch": bpe * (n_local // args.sub_batches), "issue": issue},
+                       "gather_ms": gather_ms if senv.gather and args.full else None},  # (the kernel-time pass's)
         }
-        if world == 1 and not args.no_cpu_baseline:
-            pool, labels = ds.device_pool()
-            n_cpu, s_cpu = (65536, 170) if w["kind"] == "cls" else (256, 2040)  # about 10 s of CPU work each
-            out["cpu_baseline"] = image_cpu_baseline(w, pool, labels, c, n_cpu, s_cpu)
+        if args.full:
+            out["roofline"] = image_roofline(args, w, c, n_local, log_stats, step_ms, len(timed))
+            if world == 1 and not args.no_cpu_baseline:
+                pool, labels = ds.device_pool()
+                n_cpu, s_cpu = (65536, 170) if w["kind"] == "cls" else (256, 2040)  # about 10 s of CPU work each
+                out["cpu_baseline"] = image_cpu_baseline(w, pool, labels, c, n_cpu, s_cpu)
         print(json.dumps(out), flush=True)
     env.close()
     if dist.is_initialized():
@@ -415,6 +485,41 @@ def issue_fractions(per_launch: dict, kernel_ms: float) -> dict:
     return out
 
 
+def lidar_roofline(args, w: dict, beams: int, msize: int, n_local: int, kernel_ms: float, median_ms: float,
+                   launches_timed: int, reset_ev: int, reset_steps: int) -> dict:
+    """--full: the roofline block of a LIDAR workload from the kernel-time pass: `launches_timed` launches carried
+    events (`reset_ev` of them autoreset steps), mean `kernel_ms`, median `median_ms`."""
+    step_b = BYTES_PER_ENV_STEP(beams) * (n_local // args.sub_batches)  # (the timed launch: sub-batch 0's)
+    # a reset step also writes each env's map obs (f32) and its bit-packed occupancy rows
+    reset_b = step_b + (MAP_OBS_BYTES(msize) + msize * ((msize + 63) // 64) * 8) * (n_local // args.sub_batches)
+    bytes_per_launch = (step_b * (launches_timed - reset_ev) + reset_b * reset_ev) / launches_timed
+    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
+    shape = {"num_envs": n_local, "beams": beams, "map": msize}
+    tj, tpath = pmc_table(args.workload, "lidar", shape)
+    traffic = issue = traffic_cal = None
+    if tj is not None:
+        hb = tj["hbm_bytes_per_launch"]
+        reset_b_pmc = hb.get("reset_step") or hb["step"]  # a table without a reset step: no reset in the window
+        traffic = (hb["step"] * (launches_timed - reset_ev) + reset_b_pmc * reset_ev) / launches_timed
+        issue = issue_fractions(tj["per_launch"]["step"], median_ms)
+        issue["source"] = tpath
+        # state / action loads and the 32-row occupancy windows: 8-B lanes in 256-B runs; 4-B output stores
+        traffic_cal = calibrated_traffic(tj["per_launch"]["step"], "k_seg256_8", "k_store4")
+    dj, dpath = newest_table("durations", args.workload, "lidar", shape, lambda t: "step" in t.get("per_class", {}))
+    bound, basis = derive_bound(achieved / HBM_PEAK_GBS, issue)
+    return {"bound": bound, "bound_basis": basis, "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_calibrated": traffic_cal,
+            "kernel": "k_lidar_step" + (" (+ k_maze_stream, k_maze, k_maze_paint: workgroups that exit at "
+                                        "once on ordinary steps)" if w["kind"] == "maze" else ""),
+            "kernel_ms": kernel_ms, "median_kernel_ms": median_ms,
+            "kernel_ms_rocprof": ({c: v["median_us"] / 1e3 for c, v in dj["per_class"].items()}
+                                  if dj else None), "durations_source": dpath,
+            "bytes_per_launch": bytes_per_launch, "reset_steps_timed": reset_steps,
+            "launches_timed": launches_timed, "event_every": args.event_every,
+            "traffic_source": tpath, "issue": issue}
+
+
 def run_lidar(args, world, rank, dev):
     import statistics
 
@@ -442,7 +547,7 @@ def run_lidar(args, world, rank, dev):
         return apg.make_vec(w["env_id"], num_envs=num_envs, lidar_beam_count=beams, dataset=ds, device=dev,
                             array_backend=args.array_backend, env_offset=env_offset, **kw)
 
-    senv = ShardedVectorEnv(make_local, n_total, rank, world, beams, gather=args.gather, time_gather=True,
+    senv = ShardedVectorEnv(make_local, n_total, rank, world, beams, gather=args.gather, time_gather=args.full,
                             sub_batches=args.sub_batches, gather_lag=args.gather_lag)
     env = senv.env
     ring = 128  # distinct synthetic action/prediction batches, cycled
@@ -459,8 +564,9 @@ def run_lidar(args, world, rank, dev):
         nonlocal steps_done
         if ev is not None:
             env.set_kernel_timing_events(*ev)  # (None, None): no events on this step
-        senv.step(inputs[steps_done % ring])
+        result = senv.step(inputs[steps_done % ring])
         steps_done += 1
+        return result
 
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -470,44 +576,49 @@ def run_lidar(args, world, rank, dev):
     for _ in range(args.warmup):
         step()
     senv.gather_ms()
-    ev = HipEvents(args.steps + EPISODE_PERIOD)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     # the timed window (`value`): K plain steps, no hipEvents between the launches (nor around the all-gathers)
     senv.time_gather = False
+    last = None
     t0 = time.perf_counter()
     first_timed = steps_done + 1
     for t in range(args.steps):
-        step()
+        last = step()
     if senv.gather_lag:  # (the last step's all-gather, returned one call late, is part of the window)
-        senv.flush()
+        last = senv.flush()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     senv.check_errors()
-    # the kernel-time pass (roofline and gather_ms, not `value`): K more steps, hipEvents around the step's
-    # launches on every event_every-th (an event pair adds stream packets and +6..9 us of wall to its step) and
-    # around every all-gather
-    senv.time_gather = True
-    first_ev = steps_done + 1
-    timed = [t for t in range(args.steps) if t % args.event_every == args.event_every - 1]  # steps with hipEvents
-    for t in range(args.steps):
-        step(ev.pair(t) if t % args.event_every == args.event_every - 1 else (None, None))
-    torch.cuda.synchronize(dev)
-    env.set_kernel_timing_events(None)
-    senv.check_errors()
-    per_step = [ev.elapsed_ms(i) for i in timed]
-    gather_ms = senv.gather_ms() or 0.0
-    kernel_ms = sum(per_step) / len(per_step)
-    median_ms = statistics.median(per_step)
-    # reset steps (1-based step index t with t % 101 == 0: synchronized episodes) in the timed window
-    reset_steps = sum(1 for t in range(first_timed, first_timed + args.steps) if t % EPISODE_PERIOD == 0)
+    if args.dump_outputs and rank == 0 and last is not None:  # (before later steps rewrite the output buffers)
+        dump_outputs(args.dump_outputs, last)
+    kernel_ms = median_ms = gather_ms = 0.0
+    if args.full:
+        # the kernel-time pass (roofline and gather_ms, not `value`): K more steps, hipEvents around the step's
+        # launches on every event_every-th (an event pair adds stream packets and +6..9 us of wall to its step) and
+        # around every all-gather
+        ev = HipEvents(args.steps + EPISODE_PERIOD)
+        senv.time_gather = True
+        first_ev = steps_done + 1
+        timed = [t for t in range(args.steps) if t % args.event_every == args.event_every - 1]  # steps with hipEvents
+        for t in range(args.steps):
+            step(ev.pair(t) if t % args.event_every == args.event_every - 1 else (None, None))
+        torch.cuda.synchronize(dev)
+        env.set_kernel_timing_events(None)
+        senv.check_errors()
+        per_step = [ev.elapsed_ms(i) for i in timed]
+        gather_ms = senv.gather_ms() or 0.0
+        kernel_ms = sum(per_step) / len(per_step)
+        median_ms = statistics.median(per_step)
+        # reset steps (1-based step index t with t % 101 == 0: synchronized episodes) in the timed window
+        reset_steps = sum(1 for t in range(first_timed, first_timed + args.steps) if t % EPISODE_PERIOD == 0)
 
     # one whole episode after the timed region (untimed for `value`): 100 steps + the autoreset step
     episode = None
-    if not args.no_episode:
+    if args.full and not args.no_episode:
         while steps_done % EPISODE_PERIOD:
             step()
         torch.cuda.synchronize(dev)
@@ -527,7 +638,8 @@ def run_lidar(args, world, rank, dev):
         # mean kernel time of the episode: the ordinary steps' sampled mean over 100 steps + the reset step
         ep_mean = (statistics.mean(ep[:-1]) * (EPISODE_PERIOD - 1) + ep[-1]) / EPISODE_PERIOD
         episode = [ep_s, ep[-1], statistics.median(ep[:-1]), ep_mean]
-    ev.close()
+    if args.full:
+        ev.close()
 
     if world > 1:
         tt = torch.tensor([elapsed, kernel_ms, median_ms, reset_ms, gather_ms] + (episode or [0.0] * 4),
@@ -539,26 +651,6 @@ def run_lidar(args, world, rank, dev):
 
     if rank == 0:
         value = n_total * args.steps / elapsed
-        step_b = BYTES_PER_ENV_STEP(beams) * (n_local // args.sub_batches)  # (the timed launch: sub-batch 0's)
-        # a reset step also writes each env's map obs (f32) and its bit-packed occupancy rows
-        reset_b = step_b + (MAP_OBS_BYTES(msize) + msize * ((msize + 63) // 64) * 8) * (n_local // args.sub_batches)
-        # the launches the kernel time averages over: the kernel-time pass's steps that carried events
-        reset_ev = sum(1 for t in timed if (first_ev + t) % EPISODE_PERIOD == 0)
-        bytes_per_launch = (step_b * (len(timed) - reset_ev) + reset_b * reset_ev) / len(timed)
-        achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
-        shape = {"num_envs": n_local, "beams": beams, "map": msize}
-        tj, tpath = pmc_table(args.workload, "lidar", shape)
-        traffic = issue = traffic_cal = None
-        if tj is not None:
-            hb = tj["hbm_bytes_per_launch"]
-            reset_b_pmc = hb.get("reset_step") or hb["step"]  # a table without a reset step: no reset in the window
-            traffic = (hb["step"] * (len(timed) - reset_ev) + reset_b_pmc * reset_ev) / len(timed)
-            issue = issue_fractions(tj["per_launch"]["step"], median_ms)
-            issue["source"] = tpath
-            # state / action loads and the 32-row occupancy windows: 8-B lanes in 256-B runs; 4-B output stores
-            traffic_cal = calibrated_traffic(tj["per_launch"]["step"], "k_seg256_8", "k_store4")
-        dj, dpath = newest_table("durations", args.workload, "lidar", shape, lambda t: "step" in t.get("per_class", {}))
-        bound, basis = derive_bound(achieved / HBM_PEAK_GBS, issue)
         out = {
             "metric": "env-steps/sec (vectorized step) at 1/2/4/8 MI355X + achieved HBM GB/s",
             "value": value,
@@ -579,22 +671,17 @@ def run_lidar(args, world, rank, dev):
                        "num_envs_per_gpu": n_local,
                        "num_envs_total": n_total,
                        "beams": beams, "map": f"{msize}x{msize} {w['kind']}", "max_episode_steps": 100,
-                       "reset_ms": reset_ms, "note": w["note"], "gather_ms": gather_ms if senv.gather else None,
+                       "reset_ms": reset_ms, "note": w["note"],
+                       "gather_ms": gather_ms if senv.gather and args.full else None,  # (the kernel-time pass's)
                        "packed_rows": bool(senv._packed), "gather_lag": senv.gather_lag,
                        "parallelism": f"env-shard x{world}" + (" + all-gather" if senv.gather else "") + (
                            " (pipelined: step t's batch returned with step t+1)" if senv.gather_lag else "")},
-            "roofline": {"bound": bound, "bound_basis": basis, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_calibrated": traffic_cal,
-                         "kernel": "k_lidar_step" + (" (+ k_maze_stream, k_maze, k_maze_paint: workgroups that exit at "
-                                                     "once on ordinary steps)" if w["kind"] == "maze" else ""),
-                         "kernel_ms": kernel_ms, "median_kernel_ms": median_ms,
-                         "kernel_ms_rocprof": ({c: v["median_us"] / 1e3 for c, v in dj["per_class"].items()}
-                                               if dj else None), "durations_source": dpath,
-                         "bytes_per_launch": bytes_per_launch, "reset_steps_timed": reset_steps,
-                         "launches_timed": len(timed), "event_every": args.event_every,
-                         "traffic_source": tpath, "issue": issue},
         }
+        if args.full:
+            # the launches the kernel time averages over: the kernel-time pass's steps that carried events
+            reset_ev = sum(1 for t in timed if (first_ev + t) % EPISODE_PERIOD == 0)
+            out["roofline"] = lidar_roofline(args, w, beams, msize, n_local, kernel_ms, median_ms, len(timed), reset_ev,
+                                             reset_steps)
         if episode:
             ep_s, reset_step_ms, ep_median, ep_mean = episode
             out["episode"] = {
@@ -603,7 +690,7 @@ def run_lidar(args, world, rank, dev):
                 "median_kernel_ms": ep_median, "mean_kernel_ms": ep_mean,
                 "note": "one synchronized episode after the timed steps: 100 steps + the NEXT_STEP autoreset step "
                         "(map generation of every env + map obs), wall clock"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(beams, msize, w["kind"], args.cpu_envs, args.cpu_steps,
                                                args.cpu_threads)
         print(json.dumps(out), flush=True)
@@ -768,8 +855,17 @@ def main():
     ap.add_argument("--gather-lag", type=int, default=0, choices=[0, 1],
                     help="with --gather (LIDAR): 1 = pipelined all-gather, step t's gathered batch returned with step "
                          "t+1's call (two send / receive buffers), so RCCL moves step t's rows while step t+1 runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-episode", action="store_true", help="skip the one-episode measurement after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: the kernel-time pass (roofline, "
+                         "config.gather_ms), the one-episode measurement and the CPU baseline; a plain run only sets "
+                         "up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them returned (obs, reward, terminated, "
+                         "truncated, info; rank 0's) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
+                         "(a fixed seeded sample of the rows of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-episode", action="store_true",
+                    help="--full: skip the one-episode measurement after the timed steps")
     ap.add_argument("--cpu-envs", type=int, default=None)
     ap.add_argument("--cpu-steps", type=int, default=101)
     ap.add_argument("--cpu-threads", type=int, default=None, help="OpenMP threads of the multi-thread CPU row")

@@ -96,7 +96,8 @@ def test_dry_run_rejects_an_uneven_split():
 @pytest.mark.gpu
 @pytest.mark.parametrize("gather", [False, True], ids=["shard", "gather"])
 def test_self_launch_lidar_two_ranks_one_gpu(gather):
-    args = ["--gpus", "2", "--workload", "lidar", "--num-envs", "512", "--steps", "8", "--warmup", "2",
+    # (--full: config.gather_ms comes from the kernel-time pass)
+    args = ["--gpus", "2", "--workload", "lidar", "--num-envs", "512", "--steps", "8", "--warmup", "2", "--full",
             "--dist-backend", "gloo", "--no-cpu-baseline", "--no-episode"] + (["--gather"] if gather else [])
     out = _run(args, 300)
     assert out["n_gpus"] == 2

@@ -12,7 +12,7 @@ if [ "${MAZE_PMC:-1}" = 1 ]; then
 fi
 run() {
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err
+  timeout -k 10 400 python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err
   python3 -c "
 import json; d=json.loads(open('$O/bench_$name.json').read().strip().splitlines()[-1]); r=d['roofline']; e=d.get('episode') or {}
 print('$name', '%.4g' % d['value'], 'wall %.1f us' % (d['ms_per_step']*1e3), 'kernel %.1f us' % (r['kernel_ms']*1e3), 'frac %.3f' % r['frac'], 'traffic', r.get('traffic'), 'episode %.4g' % e.get('env_steps_per_s', 0))"

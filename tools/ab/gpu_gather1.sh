@@ -5,9 +5,9 @@ R=$PWD
 O=$R/gpurun_out/r04
 mkdir -p $O
 for WL in lidar tinyimagenet-loc; do
-  timeout -k 10 200 python3 bench.py --workload $WL --steps 300 --warmup 20 --no-cpu-baseline --no-episode \
+  timeout -k 10 200 python3 bench.py --full --workload $WL --steps 300 --warmup 20 --no-cpu-baseline --no-episode \
     > $O/gather1_${WL}_plain.json 2> $O/gather1_${WL}_plain.err || exit 1
-  timeout -k 10 200 python3 bench.py --workload $WL --steps 300 --warmup 20 --no-cpu-baseline --no-episode --gather \
+  timeout -k 10 200 python3 bench.py --full --workload $WL --steps 300 --warmup 20 --no-cpu-baseline --no-episode --gather \
     > $O/gather1_${WL}.json 2> $O/gather1_${WL}.err || exit 1
 done
 [ -n "$TRACE" ] || exit 0

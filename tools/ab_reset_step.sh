@@ -19,7 +19,7 @@ for round in 1 2; do
     rm -rf $O/kt_$tag
     [ -n "$ENVSET" ] && export "$ENVSET"
     timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt_$tag -o run -- python3 $R/bench.py \
-      --steps 20 --warmup 5 --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || { echo "ab $V failed"; tail -5 $O/$tag.err; exit 1; }
+      --full --steps 20 --warmup 5 --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err || { echo "ab $V failed"; tail -5 $O/$tag.err; exit 1; }
     [ -n "$ENVSET" ] && unset "${ENVSET%%=*}"
     f=$(find $O/kt_$tag -name "*kernel_trace.csv" | head -1)
     echo "$tag $(python3 -c "

@@ -21,11 +21,11 @@ for WL in $WLS; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$WL -o run --output-format csv -- \
     python3 $R/bench.py --workload $WL --steps 20 --warmup 5 --no-cpu-baseline > $O/stats_$WL.json 2> $O/stats_$WL.err
   cd $R
-  timeout -k 10 300 python bench.py --workload $WL --steps 20 --warmup 5 > $O/bench_${WL}_driver_shape.json \
+  timeout -k 10 300 python bench.py --full --workload $WL --steps 20 --warmup 5 > $O/bench_${WL}_driver_shape.json \
     2> $O/bench_${WL}_driver_shape.err
   tail -1 $O/bench_${WL}_driver_shape.json
 done
 if [ "$1" = lidar ]; then
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
   tail -1 $O/bench_default.json
 fi

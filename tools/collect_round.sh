@@ -23,7 +23,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace -d $O/trace_$WL -o run -- \
 cd $R
 python3 tools/durations_table.py $O/trace_$WL $WL $O/trace_$WL.json > profiles/$RND/durations_$WL.json
 python3 tools/rocpd_stats.py $O/trace_$WL --csv profiles/$RND/kernel_stats_$WL.csv > /dev/null
-timeout -k 10 400 python3 bench.py --workload $WL --steps 20 --warmup 5 "$@" > $O/bench_$WL.json 2> $O/bench_$WL.err
+timeout -k 10 400 python3 bench.py --full --workload $WL --steps 20 --warmup 5 "$@" > $O/bench_$WL.json 2> $O/bench_$WL.err
 cp $O/bench_$WL.json profiles/$RND/bench_${WL}_driver_shape.json
 # profiles/ of the box's tree does not travel back: copies under gpurun_out/$RND/profiles
 mkdir -p $O/profiles && cp profiles/$RND/*_$WL* $O/profiles/

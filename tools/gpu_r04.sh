@@ -13,10 +13,10 @@ case "$1" in
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; cat $O/smoke.log; exit $rc ;;
   bench)
     WL=$2; shift 2
-    timeout -k 10 600 python bench.py --workload $WL --steps 20 --warmup 5 "$@" > $O/bench_$WL.json 2> $O/bench_$WL.err
+    timeout -k 10 600 python bench.py --full --workload $WL --steps 20 --warmup 5 "$@" > $O/bench_$WL.json 2> $O/bench_$WL.err
     rc=$?; tail -c 1500 $O/bench_$WL.json; [ $rc -eq 0 ] || tail -n 20 $O/bench_$WL.err; exit $rc ;;
   episode)
     WL=$2; shift 2
-    timeout -k 10 600 python bench.py --workload $WL --steps 300 --warmup 20 --no-cpu-baseline "$@" > $O/ep_$WL.json 2> $O/ep_$WL.err
+    timeout -k 10 600 python bench.py --full --workload $WL --steps 300 --warmup 20 --no-cpu-baseline "$@" > $O/ep_$WL.json 2> $O/ep_$WL.err
     rc=$?; tail -c 1500 $O/ep_$WL.json; [ $rc -eq 0 ] || tail -n 20 $O/ep_$WL.err; exit $rc ;;
 esac

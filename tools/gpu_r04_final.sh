@@ -20,19 +20,19 @@ case $1 in
     ;;
   lidar)
     timeout -k 10 1000 bash tools/collect_round.sh r04 lidar || { echo "collect lidar failed"; exit 1; }
-    timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --gather --steps 20 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --gather --steps 20 --warmup 5 --no-cpu-baseline \
       > $O/bench_lidar_gather_gloo2.json 2> $O/bench_lidar_gather_gloo2.err || { echo "gather line failed"; tail -5 $O/bench_lidar_gather_gloo2.err; exit 1; }
     tail -1 $O/bench_lidar_gather_gloo2.json | cut -c1-300
-    timeout -k 10 300 python bench.py --array-backend numpy --steps 20 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --array-backend numpy --steps 20 --warmup 5 --no-cpu-baseline \
       > $O/bench_lidar_numpy.json 2> $O/bench_lidar_numpy.err || { echo "numpy line failed"; tail -5 $O/bench_lidar_numpy.err; exit 1; }
     tail -1 $O/bench_lidar_numpy.json | cut -c1-300
-    timeout -k 10 300 python bench.py --gather --steps 300 --warmup 20 --no-cpu-baseline --no-episode \
+    timeout -k 10 300 python bench.py --full --gather --steps 300 --warmup 20 --no-cpu-baseline --no-episode \
       > $O/bench_lidar_gather_rccl1.json 2> $O/bench_lidar_gather_rccl1.err || { echo "rccl gather line failed"; exit 1; }
     ;;
   *)
     timeout -k 10 1000 bash tools/collect_round.sh r04 $1 || { echo "collect $1 failed"; exit 1; }
     if [ "$1" = tinyimagenet-loc ]; then
-      timeout -k 10 300 python bench.py --workload $1 --gather --steps 300 --warmup 20 --no-cpu-baseline \
+      timeout -k 10 300 python bench.py --full --workload $1 --gather --steps 300 --warmup 20 --no-cpu-baseline \
         > $O/bench_${1}_gather_rccl1.json 2> $O/bench_${1}_gather_rccl1.err || { echo "rccl gather line failed"; exit 1; }
     fi
     ;;

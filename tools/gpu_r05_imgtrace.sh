@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -v -m gpu --timeout 300 --timeout-metho
 rc=$?; tail -n 3 $O/t_image_only.log; [ $rc -eq 0 ] || { tail -n 40 $O/t_image_only.log; exit $rc; }
 cd /tmp && export TMPDIR=/tmp
 WL=${WL:-mnist}
-timeout -k 10 300 python $R/bench.py --workload $WL --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${WL}_driver.json 2> $O/bench_${WL}_driver.err || exit $?
+timeout -k 10 300 python $R/bench.py --full --workload $WL --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${WL}_driver.json 2> $O/bench_${WL}_driver.err || exit $?
 python3 -c "import json;d=json.load(open('$O/bench_${WL}_driver.json'));print('$WL driver', round(d['value']/1e6,1),'M/s', round(d['ms_per_step']*1e3,2),'us/step')"
 rm -rf $O/ht_$WL
 timeout -k 10 300 rocprofv3 --kernel-trace --hip-trace --output-format csv -d $O/ht_$WL -o run -- python3 $R/bench.py --workload $WL \
