@@ -163,6 +163,7 @@ SYMBOLS = [
     ("apg_lidar_prefetcher_stats", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     ("apg_lidar_peek_map_index", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState),
                                                 ctypes.c_uint64, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("apg_lidar_step_envs_per_group", ctypes.c_int, [ctypes.c_int]),
     ("apg_maze_frames", ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     ("apg_map_generate", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),

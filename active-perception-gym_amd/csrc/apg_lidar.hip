@@ -2429,7 +2429,8 @@ bool capturing(hipStream_t s) {
 
 extern "C" {
 
-const char *apg_version(void) { return "apgym-mi355x 0.3.0 (gfx950)"; }
+const char *apg_version(void) { return "apgym-mi355x " APG_ABI_VERSION " (gfx950)"; }
+int apg_lidar_step_envs_per_group(int num_envs) { return step_epb(num_envs); }
 const char *apg_last_error(void) { return g_err; }
 
 int apg_lidar_query_sizes(const apg_lidar_config *cfg, apg_lidar_state_sizes *o) {

@@ -188,6 +188,9 @@ typedef struct apg_lidar_state_sizes {
   size_t prefetch_bytes;                        /* apg_lidar_state.prefetch (0: the configuration has no prefetch) */
 } apg_lidar_state_sizes;
 
+/* The ABI version of this header: the struct layouts and entry points documented here ("ABI 0.x" notes mark what
+ * each minor version added).  apg_version() returns "apgym-mi355x " APG_ABI_VERSION " (gfx950)". */
+#define APG_ABI_VERSION "0.4.0"
 const char *apg_version(void);
 const char *apg_last_error(void);
 
@@ -205,6 +208,11 @@ int apg_lidar_reset(const apg_lidar_config *cfg, const apg_lidar_state *st, uint
 /* step({"action": action, "prediction": prediction}) with NEXT_STEP autoreset. */
 int apg_lidar_step(const apg_lidar_config *cfg, const apg_lidar_state *st, const float *action,
                    const float *prediction, const apg_lidar_outputs *out, apg_stream_t stream);
+
+/* Envs per k_lidar_step workgroup that apg_lidar_step launches for num_envs envs: 64 (256 threads) or 256 (1024
+ * threads; batches that still give every CU a workgroup, or the APG_STEP_EPB tuning knob).  Host only: no launch,
+ * and without a device the CU count is taken as 256.  (ABI 0.4) */
+int apg_lidar_step_envs_per_group(int num_envs);
 
 /* apg_lidar_step, additionally recording hipEvent_t `ev_begin` / `ev_end` (may be NULL) on `stream`
  * immediately before and after the fused step kernel (k_lidar_step) — used by bench.py to time the

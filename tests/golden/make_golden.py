@@ -352,6 +352,14 @@ def make_lidar_env():
     run_lidar_env("maze127_b64", fm.FloorMapDatasetMaze(127, 127), False, 64, 2, 25, 0, "uniform")
 
 
+def make_lidar_env_beams():
+    """Beam counts off the registered ids' 8 / 16 / 32 / 64: not a multiple of 4, and more than 64 (the oracle's
+    beam directions and the kernel's instances for them, pinned to the reference)."""
+    fm = refload.load("envs.floor_map")
+    run_lidar_env("rooms32_b6", fm.FloorMapDatasetRooms(), False, 6, 5, 110, 4, "wide")
+    run_lidar_env("maze21_b72", fm.FloorMapDatasetMaze(), False, 72, 3, 110, 5, "uniform")
+
+
 # --------------------------------------------------------------------------- image envs
 def _image_modules():
     pkg = refload.load_core()
@@ -836,7 +844,7 @@ def make_stream():
 
 
 SECTIONS = {"rng": make_rng, "maps": make_maps, "loss": make_loss, "scan": make_lidar_scan,
-            "lidar": make_lidar_env, "image": make_image_env,
+            "lidar": make_lidar_env, "lidar_beams": make_lidar_env_beams, "image": make_image_env,
             "sparse": make_sparse_env, "circle_square": make_circle_square,
             "light_dark": make_light_dark, "render": make_render, "hf": make_hf, "pool": make_pool,
             "stream": make_stream}

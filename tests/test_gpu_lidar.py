@@ -22,6 +22,9 @@ ENV_CASES = {
     "maze21_b8_grid": ("maze", 21, False, 8),
     "maze127_b64": ("maze", 127, False, 64),
     "maze21_b8_sparse": ("maze", 21, False, 8),  # LIDARLocMaze-sparse-v0 (SparsifyWrapper per sub-env)
+    # beam counts off the registered ids': not a multiple of 4 (scalar lidar stores), more than 64 (no staged rows)
+    "rooms32_b6": ("rooms", 32, False, 6),
+    "maze21_b72": ("maze", 21, False, 72),
     # a user FloorMapDataset subclass (make_golden.make_pool): the resident map pool (APG_MAP_POOL)
     "pool48x40_b16": ("pool", 0, False, 16),
     "pool48x40_static_b8": ("pool", 0, True, 8),
@@ -103,7 +106,11 @@ def test_device_maps_match_reference(gpu, kind, size):
 
 
 @pytest.mark.parametrize("kind,size,count", [("rooms", 64, 4096), ("rooms", 32, 2048), ("maze", 127, 256),
-                                             ("maze", 21, 2048)])
+                                             ("maze", 21, 2048),
+                                             # ragged counts: one map, full workgroups followed by a partial one
+                                             # (k_maze_stream / k_maze_big: 64 mazes per group, the paints: 4)
+                                             ("rooms", 32, 1), ("rooms", 32, 67), ("maze", 21, 1), ("maze", 21, 67),
+                                             ("maze", 21, 257), ("maze", 127, 67), ("maze", 301, 65)])
 def test_device_maps_match_oracle_random_idx(gpu, oracle_mod, kind, size, count):
     import ap_gym_amd as ap
 
@@ -117,7 +124,8 @@ def test_device_maps_match_oracle_random_idx(gpu, oracle_mod, kind, size, count)
 @pytest.mark.parametrize("h,w,bp,count", [(21, 21, 0.5, 512), (21, 35, 0.0, 512), (63, 63, 0.3, 256),
                                            (127, 127, 0.7, 64), (3, 3, 1.0, 16), (127, 9, 1.0, 64),
                                            (255, 255, 1.0, 32), (255, 101, 0.6, 32), (301, 301, 1.0, 16),
-                                           (257, 9, 0.5, 32), (11, 511, 1.0, 16), (301, 275, 0.4, 8)])
+                                           (257, 9, 0.5, 32), (11, 511, 1.0, 16), (301, 275, 0.4, 8),
+                                           (63, 35, 0.4, 131)])
 def test_device_maze_branching_matches_oracle(gpu, oracle_mod, h, w, bp, count):
     """branching_prob < 1 (rng.random() draws decide later branches; mazes need not be perfect, so the
     stream consumption differs from the bp = 1 mazes the stream length is sized for) and odd rectangles."""
@@ -436,6 +444,114 @@ def test_long_range_matches_oracle(gpu, oracle_mod, kind, size, static, beams, l
         assert np.array_equal(term, ref.terminated.astype(bool)), t
         if not static:
             assert np.array_equal(obs["map"][..., 0], ref.map), t
+    env.close()
+
+
+def _run_against_oracle(env, ref, seed, steps, action_seed):
+    """reset(seed) and `steps` steps of env (numpy backend) against the oracle env: reset lidar and map, and per
+    step lidar, odometry, time_step, reward, terminated and map.  Returns how often each env reset."""
+    n = ref.n
+    obs, _ = env.reset(seed=seed)
+    ref.reset(seed)
+    assert np.array_equal(obs["lidar"], ref.lidar)
+    assert np.array_equal(obs["map"][..., 0], ref.map)
+    rng = np.random.default_rng(action_seed)
+    resets = np.zeros(n, int)
+    for t in range(steps):
+        a = rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+        p = rng.uniform(-1, 1, (n, 2)).astype(np.float32)
+        obs, rew, term, trunc, info = env.step({"action": a, "prediction": p})
+        ref.step(a, p)
+        assert np.array_equal(obs["lidar"], ref.lidar), t
+        assert np.array_equal(obs["odometry"], ref.odometry), t
+        assert np.array_equal(obs["time_step"], ref.time_step), t
+        assert np.array_equal(rew, ref.reward, equal_nan=True), t
+        assert np.array_equal(term, ref.terminated.astype(bool)), t
+        assert np.array_equal(obs["map"][..., 0], ref.map), t
+        resets += info.get("_map_idx", np.zeros(n, bool))
+    assert not ref.no_free_cell()
+    return resets
+
+
+@pytest.mark.parametrize("kind,size,lidar_range,beams,backend",
+                         [("rooms", 32, 5.0, b, "numpy") for b in (1, 3, 6, 30, 63, 65, 72, 100)]
+                         + [("maze", 21, 5.0, 6, "numpy"), ("maze", 21, 5.0, 72, "numpy"),
+                            ("rooms", 64, 12.0, 6, "numpy"), ("rooms", 64, 12.0, 72, "numpy"),
+                            ("rooms", 32, 5.0, 6, "torch")])
+def test_beam_counts_match_oracle(gpu, oracle_mod, kind, size, lidar_range, beams, backend):
+    """Beam counts off {8, 16, 32, 64}: not a multiple of 4 (the scalar lidar store loop instead of the 16-byte
+    stores), one, and more than MAX_STAGED_BEAMS = 64 (the phase 2 that walks in place and stores straight to global
+    memory); on the fused rooms instance, on mazes (pre-test off: the implicit queue) and at range 12 (the
+    rows-from-global-memory instance).  N = 70: a full 64-env workgroup and a partial one; 105 steps (one
+    autoreset).  The torch row: the torch backend's dense outputs against the numpy backend's output block, which
+    the other rows hold to the oracle."""
+    import ap_gym_amd as ap
+
+    n = 70
+    if backend == "torch":
+        return _torch_backend_matches_numpy_backend(ap, gpu, n, size, beams)
+    env = ap.LIDARLocalization2DVectorEnv(num_envs=n, dataset=_ds(ap, kind, size), lidar_beam_count=beams,
+                                          lidar_range=lidar_range, device=gpu)
+    ref = oracle_mod.OracleLidarVectorEnv(n, kind, size, False, 0, beams, lidar_range=lidar_range)
+    resets = _run_against_oracle(env, ref, 13, 105, 8)
+    assert resets.min() >= 1
+    env.close()
+
+
+def _torch_backend_matches_numpy_backend(ap, gpu, n, size, beams):
+    import torch
+
+    kw = dict(num_envs=n, dataset=ap.FloorMapDatasetRooms(size, size), lidar_beam_count=beams, device=gpu)
+    e_np = ap.LIDARLocalization2DVectorEnv(**kw)
+    e_t = ap.LIDARLocalization2DVectorEnv(array_backend="torch", **kw)
+    o1, _ = e_np.reset(seed=13)
+    o2, _ = e_t.reset(seed=13)
+    assert np.array_equal(o1["lidar"], o2["lidar"].cpu().numpy())
+    rng = np.random.default_rng(8)
+    for t in range(105):
+        a = rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+        p = rng.uniform(-1, 1, (n, 2)).astype(np.float32)
+        o1, r1, te1, tr1, i1 = e_np.step({"action": a, "prediction": p})
+        o2, r2, te2, tr2, i2 = e_t.step({"action": torch.from_numpy(a).to(gpu), "prediction": torch.from_numpy(p).to(gpu)})
+        for k in ("lidar", "odometry", "time_step", "map"):
+            assert np.array_equal(o1[k], o2[k].cpu().numpy()), (t, k)
+        assert np.array_equal(r1, r2.cpu().numpy()), t
+        assert np.array_equal(te1, te2.cpu().numpy()), t
+    e_t.check_errors()
+    e_np.close()
+    e_t.close()
+
+
+@pytest.mark.parametrize("n", [1, 65, 191])
+@pytest.mark.parametrize("case", ["rooms32", "pool33", "rooms64_r12", "rooms64_mr24", "maze21_limit7"])
+def test_ragged_batch_matches_oracle(gpu, oracle_mod, case, n):
+    """Batches that are no multiple of the 64-env workgroup: one env, one full workgroup plus one env, two full
+    workgroups plus 63 (the tail guards of the window loads, phases 1, 2a, 2b and the stores, and of the map and
+    reset kernels), on the fused rooms and pool instances, the rows-from-global-memory instance, k_lidar_reset plus
+    the unfused step, and the prefetched mazes."""
+    import ap_gym_amd as ap
+
+    kw, okw, steps, kind, size, beams = {}, {}, 110, "rooms", 32, 16
+    if case == "pool33":
+        from test_gpu_lidar_pool import random_pool
+
+        maps = random_pool(9, 33, 33, 14)
+        kind, size, beams, ds, okw = "pool", 0, 8, UserFloorMaps(maps), dict(pool=maps)
+    elif case == "rooms64_r12":
+        size, kw, okw = 64, dict(lidar_range=12.0), dict(lidar_range=12.0)
+    elif case == "rooms64_mr24":
+        size, okw = 64, dict(max_rooms=24)
+    elif case == "maze21_limit7":
+        kind, size, beams, steps = "maze", 21, 8, 40
+        kw, okw = dict(max_episode_steps=7, prefetch=True), dict(step_limit=7)
+    if case != "pool33":
+        ds = ap.FloorMapDatasetRooms(64, 64, max_rooms=24) if case == "rooms64_mr24" else _ds(ap, kind, size)
+    env = ap.LIDARLocalization2DVectorEnv(num_envs=n, dataset=ds, lidar_beam_count=beams, device=gpu, **kw)
+    if case == "maze21_limit7":
+        assert env._prefetcher
+    ref = oracle_mod.OracleLidarVectorEnv(n, kind, size, False, 0, beams, **okw)
+    resets = _run_against_oracle(env, ref, 17 + n, steps, 5)
+    assert resets[-1] >= 1  # the last env of the partial workgroup went through an autoreset
     env.close()
 
 

@@ -29,6 +29,33 @@ def test_capi_library_exports_every_declared_symbol():
     assert _native.lib().apg_version().startswith(b"apgym-mi355x")
 
 
+def test_capi_version_is_the_one_the_header_names():
+    """apg_version() is how a caller detects the struct layouts: its version is the header's APG_ABI_VERSION, and
+    that is the newest "ABI x.y" the header's field notes document."""
+    from ap_gym_amd import _native
+
+    src = open(os.path.join(ROOT, "include", "apgym_capi.h")).read()
+    (macro,) = re.findall(r'^#define\s+APG_ABI_VERSION\s+"(\d+\.\d+\.\d+)"', src, flags=re.M)
+    noted = max(tuple(int(x) for x in m) for m in re.findall(r"\bABI (?:<= )?(\d+)\.(\d+)", src))
+    assert tuple(int(x) for x in macro.split(".")[:2]) == noted
+    assert macro == "0.4.0"
+    got = re.fullmatch(rb"apgym-mi355x (\d+\.\d+\.\d+) \(gfx950\)", _native.lib().apg_version())
+    assert got and got.group(1).decode() == macro
+
+
+def test_step_envs_per_group_is_a_host_query():
+    """apg_lidar_step_envs_per_group: what the step launcher picks (64, or 256 once every CU still gets a workgroup;
+    256 CUs where no device answers), without a launch."""
+    from ap_gym_amd import _native
+
+    fn = _native.lib().apg_lidar_step_envs_per_group
+    if os.environ.get("APG_STEP_EPB") in ("64", "256"):
+        assert fn(1) == fn(1 << 20) == int(os.environ["APG_STEP_EPB"])
+    else:
+        assert fn(1) == 64 and fn(300) == 64 and fn(1 << 20) == 256
+        assert all(fn(n) in (64, 256) for n in (65535, 65536, 77824))
+
+
 def test_fast_call_module_reaches_the_c_abi():
     """_apgfast (csrc/apg_pyfast.cpp): the per-step C-ABI calls without ctypes marshalling.  Invalid configurations
     return the C ABI's validation error before any HIP call, so this runs without a GPU."""

@@ -20,6 +20,9 @@ ENV_CASES = {
     "maze21_b8_grid": ("maze", 21, False, 8),
     "maze127_b64": ("maze", 127, False, 64),
     "maze21_b8_sparse": ("maze", 21, False, 8),  # LIDARLocMaze-sparse-v0 (SparsifyWrapper per sub-env)
+    # beam counts off the registered ids': not a multiple of 4 (scalar lidar stores), more than 64 (no staged rows)
+    "rooms32_b6": ("rooms", 32, False, 6),
+    "maze21_b72": ("maze", 21, False, 72),
     # a user FloorMapDataset subclass of fixed maps (48 wide x 40 high; 36 x 36 with open borders)
     "pool48x40_b16": ("pool", 0, False, 16),
     "pool48x40_static_b8": ("pool", 0, True, 8),
