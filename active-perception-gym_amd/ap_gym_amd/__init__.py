@@ -36,6 +36,7 @@ from .loss_fn import (  # noqa: F401
     WeightedLossFn,
     ZeroLossFn,
 )
+from .map_bits import unpack_map_bits  # noqa: F401
 from .registration import make_vec, register, registry  # noqa: F401
 from .spaces import ActivePerceptionActionSpace, ImageSpace, LogitSpace  # noqa: F401
 

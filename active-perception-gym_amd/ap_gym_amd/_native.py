@@ -30,6 +30,11 @@ APG_ERR_OOB_Y = 8
 APG_ERR_OOB_X = 16
 APG_ERR_PREFETCH = 32
 APG_ERR_NO_FREE_CELL = 64
+APG_ERR_INDEX = 128  # apg_lidar_unpack_maps: a map id outside [0, n_src) (raised as IndexError)
+APG_UNPACK_F32 = 0
+APG_UNPACK_F16 = 1
+APG_UNPACK_BF16 = 2
+APG_UNPACK_U8 = 3
 APG_MAP_ROOMS = 0
 APG_MAP_MAZE = 1
 APG_MAP_POOL = 2
@@ -169,6 +174,8 @@ SYMBOLS = [
                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     ("apg_lidar_scan_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp,
                                             _vp]),
+    ("apg_lidar_unpack_maps", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_float, _vp, _vp, _vp]),
     ("apg_lidar_render_track", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp,
                                               ctypes.POINTER(LidarOutputs), ctypes.POINTER(LidarRenderState), _vp]),
     ("apg_rng_draws", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -38,6 +38,19 @@ Two I/O modes (constructor `array_backend`), inputs of either type are accepted:
                        are persistent buffers overwritten by the next step (gymnasium's copy=False
                        contract, the default here: copy=None -> False); pass copy=True to get fresh
                        tensors.  NaN errors are raised lazily (at a later step) unless strict_errors=True.
+
+Two forms of the map observation (constructor `map_obs`, dynamic maps only):
+  "dense" (default) -> obs["map"] float32 [N, H, W, 1], 0 or 1/255 per cell, like the reference.
+  "bits"            -> obs["map"] is the occupancy rows of every env, [N, H, wpr] with wpr = ceil(W / 64) 64-bit words
+                       (torch int64, numpy uint64): bit `x & 63` of word `x >> 6` of row `y` is cell (y, x), 1 = wall,
+                       i.e. np.unpackbits(rows.view(np.uint8), bitorder="little") per row.  The padding bits at
+                       x >= W are unspecified and consumers must ignore them.  32x smaller than the dense form, and
+                       no dense buffer exists: a reset writes no map observation at all.  With the torch backend and
+                       copy=False, obs["map"] (and device_outputs()["map"]) is a VIEW OF THE ENV'S OWN STATE, the
+                       rows the LIDAR scans read: unlike every other output, writing into it corrupts the env
+                       (copy=True returns a clone).  The numpy backend keeps the host-mirror semantics of the dense
+                       form.  `env.unpack_maps(env_ids, dtype=...)` / `ap_gym_amd.unpack_map_bits` (map_bits.py)
+                       expand chosen maps to dense maps of any of float32 / float16 / bfloat16 / uint8 on the device.
 """
 
 from __future__ import annotations
@@ -50,6 +63,7 @@ import numpy as np
 from . import _native as N
 from .floor_map import FloorMapDataset, FloorMapDatasetMaze, FloorMapDatasetRooms, as_floor_map_dataset
 from .loss_fn import WeightedLossFn, affine_f32, regression_loss
+from .map_bits import host_words_np, unpack_map_bits, words_per_row
 from .spaces import ActivePerceptionActionSpace, Box, Dict, ImageSpace, batch_space
 from .vector_env import VectorEnv
 
@@ -170,11 +184,15 @@ def torch_index(idx: np.ndarray, device):
     return torch.as_tensor(idx, dtype=torch.int64, device=device)
 
 
-def lidar_spaces(num_envs: int, height: int, width: int, beams: int, static_map: bool, sparse: bool) -> dict:
+def lidar_spaces(num_envs: int, height: int, width: int, beams: int, static_map: bool, sparse: bool,
+                 map_obs: str = "dense") -> dict:
     """Spaces and loss of the LIDAR ids (lidar_localization2d.py:144-227, time_limit.py:64-70,
-    active_regression_env.py:55-76; sparse: sparsify_wrapper.py:93-127)."""
+    active_regression_env.py:55-76; sparse: sparsify_wrapper.py:93-127).  map_obs="bits": the map observation is
+    the occupancy rows, uint64 [height, ceil(width / 64)] (map_bits.py)."""
     obs = {"lidar": Box(0, 1, (beams,), np.float32), "odometry": Box(-1, 1, (2,), np.float32)}
-    if not static_map:
+    if not static_map and map_obs == "bits":
+        obs["map"] = Box(0, np.iinfo(np.uint64).max, (height, words_per_row(width)), np.uint64)
+    elif not static_map:
         obs["map"] = ImageSpace(width=width, height=height, channels=1)
     obs["time_step"] = Box(-1.0, 1.0, (), np.float32)
     single_obs = Dict(obs)
@@ -200,11 +218,17 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
                  max_episode_steps: int = 100, device=None, env_offset: int = 0, copy: bool | None = None,
                  strict_errors: bool = False, array_backend: str = "numpy", log_stats: bool = False,
                  sparse: bool = False, render_envs=None, sparse_reset_info: bool = False, packed_outputs: bool = False,
-                 vector_stats: str = "list", frozen_maps: bool | None = None, obs_snapshot: str = "copy"):
+                 vector_stats: str = "list", frozen_maps: bool | None = None, obs_snapshot: str = "copy",
+                 map_obs: str = "dense"):
         import torch
 
         if render_mode not in self.metadata["render_modes"]:
             raise ValueError(f"Invalid render mode: {render_mode}")
+        if map_obs not in ("dense", "bits"):
+            raise ValueError("map_obs must be 'dense' (float32 [N, H, W, 1]) or 'bits' (the occupancy rows)")
+        if map_obs == "bits" and static_map:
+            raise ValueError("map_obs='bits' needs dynamic maps: the static ids have no 'map' observation")
+        self.map_obs = map_obs
         if dataset is None:
             dataset = FloorMapDatasetRooms()
         # any other FloorMapDataset (a reference subclass included) runs from a resident map pool (APG_MAP_POOL)
@@ -237,7 +261,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             raise ValueError("LIDARLocalization2DVectorEnv runs on a GPU device (no CPU fallback)")
         h, w = dataset.map_height, dataset.map_width
 
-        sp = lidar_spaces(self.num_envs, h, w, self.lidar_beam_count, self.static_map, self.sparse)
+        sp = lidar_spaces(self.num_envs, h, w, self.lidar_beam_count, self.static_map, self.sparse, self.map_obs)
         inner_loss = sp.pop("inner_loss")
         for k, v in sp.items():
             setattr(self, k, v)
@@ -294,7 +318,8 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             lidar=t.zeros((n, B), dtype=t.float32, device=dev),
             odometry=t.zeros((n, 2), dtype=t.float32, device=dev),
             time_step=t.zeros(n, dtype=t.float32, device=dev),
-            map_obs=None if self.static_map else t.zeros((n, h, w, 1), dtype=t.float32, device=dev),
+            map_obs=(None if self.static_map or self.map_obs == "bits"  # bits: no dense buffer, NULL in the C ABI
+                     else t.zeros((n, h, w, 1), dtype=t.float32, device=dev)),
             reward=t.zeros(n, dtype=t.float64, device=dev),
             terminated=t.zeros(n, dtype=t.bool, device=dev),
             truncated=t.zeros(n, dtype=t.bool, device=dev),
@@ -327,6 +352,10 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             self._out_block = t.zeros(nbytes, dtype=t.uint8, device=dev)
             self._t.update(block_views(self._out_block, self._block_layout))
         T = self._t
+        # map_obs="bits": the observation is the env's own occupancy rows, [n, h, wpr] (a view, not a buffer)
+        self._map_bits = T["occ"].view(n, h, words_per_row(w)) if self.map_obs == "bits" else None
+        # the device tensor behind obs["map"]: the dense buffer, or the occupancy rows themselves (None: static maps)
+        self._map_t = T["map_obs"] if self._map_bits is None else self._map_bits
         # the prefetcher (C++ in the library): side stream, pinned per-step reset counts, batch events
         self._prefetcher = None
         if T["prefetch"] is not None:
@@ -508,7 +537,54 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         out = {k: T[k] for k in ("lidar", "odometry", "time_step", "reward", "terminated", "truncated", "base_reward",
                                  "target", "loss", "info_mask", "reset_mask")}
         if not self.static_map:
-            out["map"] = T["map_obs"]
+            out["map"] = self._map_t
+        return out
+
+    def _map_np(self, t) -> np.ndarray:
+        """numpy form of a host map tensor (bits: torch's int64 words as numpy uint64).  In both forms the array's base
+        is the tensor, not another ndarray, so every slice or view a caller keeps refers to this very array: that is
+        what _map_refresh's reference counts rely on."""
+        return t.numpy() if self._map_bits is None else host_words_np(t)
+
+    def unpack_maps(self, env_ids=None, *, dtype=None, wall: float | None = None, out=None):
+        """map_obs="bits": dense maps [M, H, W, 1] of `dtype` of the sub-envs `env_ids` (any order, duplicates allowed;
+        None: every sub-env), expanded from the env's current occupancy rows by the device kernel -- unpack_map_bits
+        (map_bits.py) on the env's own rows.  With the defaults (float32, wall 1/255) the result equals the dense
+        obs["map"].  An id outside [0, num_envs) yields an all-zero map and raises IndexError through check_errors()
+        (torch backend: lazily, like the NaN checks; numpy backend: at once).  The numpy backend accepts numpy ids
+        and dtypes and returns numpy arrays (`out`, a numpy array, is filled and returned); the torch backend
+        returns device tensors (`out`: a device tensor to write into)."""
+        import torch
+
+        if self._closed:
+            raise RuntimeError("environment is closed")
+        if self._map_bits is None:
+            raise RuntimeError("unpack_maps() needs map_obs='bits' (map_obs='dense' returns dense maps already)")
+        if isinstance(env_ids, torch.Tensor):  # any integer tensor on any device
+            if env_ids.is_floating_point() or env_ids.is_complex() or env_ids.dtype == torch.bool:
+                raise TypeError(f"env_ids must hold integers, got {env_ids.dtype}")
+            env_ids = env_ids.to(device=self._dev, dtype=torch.int64).reshape(-1).contiguous()
+        elif env_ids is not None:  # a numpy array, a list, one int
+            ids = np.asarray(env_ids)
+            if ids.size and ids.dtype.kind not in "iu":
+                raise TypeError(f"env_ids must hold integers, got {ids.dtype}")
+            env_ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1), device=self._dev)
+        w = self.dataset.map_width
+        if self.array_backend != "numpy":
+            return unpack_map_bits(self._map_bits, w, env_ids, dtype=dtype, wall=wall, out=out, err=self._t["err"])
+        if dtype is not None and not isinstance(dtype, torch.dtype):
+            by_np = {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16,
+                     np.dtype(np.uint8): torch.uint8}
+            if np.dtype(dtype) not in by_np:
+                raise TypeError(f"dtype must be float32, float16 or uint8 (or a torch dtype), got {dtype}")
+            dtype = by_np[np.dtype(dtype)]
+        if dtype == torch.bfloat16:
+            raise TypeError("numpy has no bfloat16: use the torch backend or ap_gym_amd.unpack_map_bits")
+        res = unpack_map_bits(self._map_bits, w, env_ids, dtype=dtype, wall=wall, err=self._t["err"]).cpu().numpy()
+        self.check_errors(block=True)
+        if out is None:
+            return res
+        np.copyto(out, res.reshape(out.shape), casting="no")
         return out
 
     def _launch_step(self, a_t, p_t):
@@ -544,6 +620,8 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             raise ValueError("high <= 0")
         if bits & N.APG_ERR_PREFETCH:
             raise N.ApgError("an autoreset found no prefetched map (prefetch protocol violated)")
+        if bits & N.APG_ERR_INDEX:
+            raise IndexError("unpack_maps(): an env id outside [0, num_envs)")
 
     def check_errors(self, block: bool = True):
         """Raise the reference's exception for any error flagged by the kernels so far."""
@@ -743,7 +821,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         c = (lambda x: x.clone()) if self.copy else (lambda x: x)
         obs = {"lidar": c(T["lidar"]), "odometry": c(T["odometry"])}
         if not self.static_map:
-            obs["map"] = c(T["map_obs"])
+            obs["map"] = c(self._map_t)
         obs["time_step"] = c(T["time_step"])
         return obs
 
@@ -810,17 +888,17 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
 
         if self.static_map:
             return None
-        T = self._t
+        src = self._map_t  # float32 [N, H, W, 1], or (map_obs="bits") the int64 rows [N, H, wpr]: 32x smaller
         if self._map_host is None:
-            self._map_host = torch.empty(tuple(T["map_obs"].shape), dtype=torch.float32).pin_memory()
+            self._map_host = torch.empty(tuple(src.shape), dtype=src.dtype).pin_memory()
             reset_mask = None
         changed = reset_mask is None or bool(reset_mask.any())
         if reset_mask is None or reset_mask.all():
-            self._map_host.copy_(T["map_obs"])
+            self._map_host.copy_(src)
         elif changed:
             idx = np.nonzero(reset_mask)[0]
-            self._map_host.numpy()[idx] = T["map_obs"][torch_index(idx, self.device)].cpu().numpy()
-        m = self._map_host.numpy()
+            self._map_host.numpy()[idx] = src[torch_index(idx, self.device)].cpu().numpy()
+        m = self._map_np(self._map_host)
         if not self.copy:
             return m
         if self.obs_snapshot == "copy":
@@ -830,8 +908,8 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
                     blk = b
                     break
             if blk is None:
-                t = torch.empty(tuple(self._map_host.shape), dtype=torch.float32)
-                blk = (t, t.numpy())
+                t = torch.empty(tuple(self._map_host.shape), dtype=self._map_host.dtype)
+                blk = (t, self._map_np(t))
                 if len(self._map_copies) < self.MAP_COPIES:
                     self._map_copies.append(blk)
             blk[0].copy_(self._map_host)  # whole: the caller may have written into an earlier hand-out of it
@@ -839,7 +917,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         if changed or self._map_snapshot is None:
             # torch's CPU copy runs on the intra-op thread pool (numpy's m.copy() is one thread: 3-4x slower at
             # the 1 GB of a cfg-2 episode end)
-            self._map_snapshot = self._map_host.clone().numpy()
+            self._map_snapshot = self._map_np(self._map_host.clone())
             self._map_snapshot.flags.writeable = False
         return self._map_snapshot
 
@@ -911,6 +989,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
                 self._streamer.close()
                 self._streamer = None
             self._t = {}
+            self._map_t = self._map_bits = None
             self._h = None  # the op handle keeps every state/output buffer alive
             self._c_args = None
             self.output_rows = self._out_block = None

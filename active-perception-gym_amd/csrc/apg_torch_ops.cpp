@@ -10,6 +10,7 @@
 //   torch.ops.apgym.lidar_step(LidarEnv env, Tensor action, Tensor prediction) -> ()
 //   torch.ops.apgym.image_reset(ImageEnv env) -> ()
 //   torch.ops.apgym.image_step(ImageEnv env, Tensor action, Tensor prediction, int t, int prev_done) -> ()
+//   torch.ops.apgym.unpack_map_bits(Tensor bits, int width, Tensor? env_ids, Tensor out, float wall, Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -173,6 +174,50 @@ void image_step(const c10::intrusive_ptr<ImageEnv> &e, const at::Tensor &action,
         "apg_image_step");
 }
 
+// bits: int64 [n_src, H, ceil(width / 64)] occupancy rows (apg_lidar_state.occ's layout); out: the [M, H, width(, 1)]
+// maps in its own dtype (float32 / float16 / bfloat16 / uint8), M = len(env_ids) or n_src; err: the int32 [1] error word
+// a bad id is flagged in (APG_ERR_INDEX), or None
+void unpack_map_bits(const at::Tensor &bits, int64_t width, const c10::optional<at::Tensor> &env_ids, at::Tensor out,
+                     double wall, const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(bits.is_cuda(), "bits must be on a GPU device, got ", bits.device());
+  const at::Device dev = bits.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(bits.scalar_type() == at::kLong && bits.dim() == 3 && bits.is_contiguous(),
+              "bits must be a contiguous int64 [n_src, H, ceil(width / 64)] tensor");
+  TORCH_CHECK(width >= 1 && width <= 511 && bits.size(2) == (width + 63) / 64, "bits has ", bits.size(2),
+              " words per row, width ", width, " needs ", (width + 63) / 64, " (width 1..511)");
+  const int64_t n_src = bits.size(0), h = bits.size(1);
+  TORCH_CHECK(h >= 1 && h <= 511, "map height must be 1..511, got ", h);
+  int64_t count = n_src;
+  const int64_t *ids = nullptr;
+  if (env_ids.has_value() && env_ids->defined()) {
+    TORCH_CHECK(env_ids->device() == dev && env_ids->scalar_type() == at::kLong && env_ids->dim() == 1 &&
+                    env_ids->is_contiguous(),
+                "env_ids must be a contiguous 1-d int64 tensor on ", dev);
+    count = env_ids->numel();
+    ids = count ? env_ids->data_ptr<int64_t>() : nullptr;
+  }
+  TORCH_CHECK(out.device() == dev && out.is_contiguous(), "out must be a contiguous tensor on ", dev);
+  TORCH_CHECK(out.numel() == count * h * width, "out must have ", count * h * width, " elements, got ", out.numel());
+  int dtype;
+  switch (out.scalar_type()) {
+    case at::kFloat: dtype = APG_UNPACK_F32; break;
+    case at::kHalf: dtype = APG_UNPACK_F16; break;
+    case at::kBFloat16: dtype = APG_UNPACK_BF16; break;
+    case at::kByte: dtype = APG_UNPACK_U8; break;
+    default: TORCH_CHECK(false, "out must be float32, float16, bfloat16 or uint8, got ", out.scalar_type());
+  }
+  uint32_t *errp = nullptr;
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    errp = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  check(apg_lidar_unpack_maps(reinterpret_cast<const uint64_t *>(ptr(bits)), n_src, (int)h, (int)width, ids, count, dtype,
+                              (float)wall, ptr(out), errp, stream_of(dev)),
+        "apg_lidar_unpack_maps");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -186,4 +231,7 @@ TORCH_LIBRARY(apgym, m) {
   m.def("image_step(__torch__.torch.classes.apgym.ImageEnv env, Tensor action, Tensor prediction, int t, "
         "int prev_done) -> ()",
         image_step);
+  m.def("unpack_map_bits(Tensor bits, int width, Tensor? env_ids, Tensor(a!) out, float wall, Tensor(b!)? err=None) "
+        "-> ()",
+        unpack_map_bits);
 }

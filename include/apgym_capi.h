@@ -80,6 +80,7 @@ extern "C" {
 #define APG_ERR_PREFETCH 32u      /* a maze autoreset found no prefetched map (prefetch protocol violated) */
 #define APG_ERR_NO_FREE_CELL 64u  /* a pool map without a free cell was drawn: numpy's integers(0, 0) raises
                                      ValueError("high <= 0") in reset (lidar_localization2d.py:302-303) */
+#define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps: a map id outside [0, n_src) (raised as IndexError) */
 
 #define APG_MAP_ROOMS 0
 #define APG_MAP_MAZE 1
@@ -267,6 +268,21 @@ int apg_map_generate(int map_kind, const uint64_t *idx, int n, int h, int w, int
 /* n segments seg[n][4] = (px, py, qx, qy) against map map_index[n] of occ[*][h][wpr]. */
 int apg_lidar_scan_batch(const uint64_t *occ, const int32_t *map_index, int h, int w,
                          const float *seg, int n, float *dist, int32_t *kind, apg_stream_t stream);
+
+/* Occupancy bit rows -> dense maps (an addition to ABI 0.4; no struct changes).  occ is [n_src][height][wpr] with
+ * wpr = ceil(width / 64), the layout of apg_lidar_state.occ: bit x & 63 of word x >> 6 of row y is cell (y, x),
+ * 1 = wall; the padding bits at x >= width are never read into the output.  Output map m (of count) is map
+ * env_ids[m] of occ (env_ids NULL: map m; duplicates and any order are allowed), its cell (y, x) `wall` where the bit
+ * is set and 0 elsewhere.  `wall` is converted once, round-to-nearest-even, to the element type; for APG_UNPACK_U8 it
+ * must be an integer in 0..255.  dst is [count][height][width] of that type at any alignment natural for it.  An id
+ * outside [0, n_src) is never read: its map is all zeros and APG_ERR_INDEX is OR-ed into *err (err may be NULL).
+ * height and width are 1..511; count == 0 launches nothing. */
+#define APG_UNPACK_F32 0
+#define APG_UNPACK_F16 1
+#define APG_UNPACK_BF16 2
+#define APG_UNPACK_U8 3
+int apg_lidar_unpack_maps(const uint64_t *occ, int64_t n_src, int height, int width, const int64_t *env_ids,
+                          int64_t count, int dtype, float wall, void *dst, uint32_t *err, apg_stream_t stream);
 
 /* ---------------------------------------------------------------- LIDAR render path (not the hot path)
  * Render-only state of the tracked sub-envs: what LIDARLocalization2DEnv keeps for render()
