@@ -30,7 +30,13 @@ APG_ERR_OOB_Y = 8
 APG_ERR_OOB_X = 16
 APG_ERR_PREFETCH = 32
 APG_ERR_NO_FREE_CELL = 64
-APG_ERR_INDEX = 128  # apg_lidar_unpack_maps: a map id outside [0, n_src) (raised as IndexError)
+APG_ERR_INDEX = 128  # apg_lidar_unpack_maps / apg_lidar_scan_poses: a map id outside [0, n_src) (raised as IndexError)
+APG_ERR_BAD_POSE = 256  # apg_lidar_scan_poses: a pose with a non-finite coordinate (raised as ValueError)
+# k_scan_poses' work split (csrc/apg_scan_poses.hip SP_TILE, SP_MAX_MPW, SP_MAX_GRID): rays per workgroup pass, pose
+# sets a workgroup takes at once when a set is small, workgroups per launch
+SCAN_POSES_TILE = 256
+SCAN_POSES_MAX_MPW = 32
+SCAN_POSES_MAX_GRID = 8192
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -92,6 +98,13 @@ class LidarRenderState(ctypes.Structure):
     _fields_ = [("num_tracked", ctypes.c_int32), ("scan_points", ctypes.c_int32)] + [
         (n, _vp) for n in ("env", "scan_xy", "scan_norm", "obs_map", "traj", "traj_len", "pose", "has_last",
                            "lidar_dist")]
+
+
+class ScanPosesArgs(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("occ", "map_ids", "poses", "beam_dirs", "observed", "scan", "score", "err")] + [
+        ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ("height", "width", "k", "beams", "normalize")] + [
+        ("lidar_range", ctypes.c_float)]
 
 
 class LidarSizes(ctypes.Structure):
@@ -176,6 +189,7 @@ SYMBOLS = [
                                             _vp]),
     ("apg_lidar_unpack_maps", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_float, _vp, _vp, _vp]),
+    ("apg_lidar_scan_poses", ctypes.c_int, [ctypes.POINTER(ScanPosesArgs), _vp]),
     ("apg_lidar_render_track", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp,
                                               ctypes.POINTER(LidarOutputs), ctypes.POINTER(LidarRenderState), _vp]),
     ("apg_rng_draws", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

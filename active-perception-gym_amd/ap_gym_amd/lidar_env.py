@@ -64,6 +64,7 @@ from . import _native as N
 from .floor_map import FloorMapDataset, FloorMapDatasetMaze, FloorMapDatasetRooms, as_floor_map_dataset
 from .loss_fn import WeightedLossFn, affine_f32, regression_loss
 from .map_bits import host_words_np, unpack_map_bits, words_per_row
+from .scan_poses import lidar_pose_scores, lidar_scan_poses
 from .spaces import ActivePerceptionActionSpace, Box, Dict, ImageSpace, batch_space
 from .vector_env import VectorEnv
 
@@ -560,15 +561,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             raise RuntimeError("environment is closed")
         if self._map_bits is None:
             raise RuntimeError("unpack_maps() needs map_obs='bits' (map_obs='dense' returns dense maps already)")
-        if isinstance(env_ids, torch.Tensor):  # any integer tensor on any device
-            if env_ids.is_floating_point() or env_ids.is_complex() or env_ids.dtype == torch.bool:
-                raise TypeError(f"env_ids must hold integers, got {env_ids.dtype}")
-            env_ids = env_ids.to(device=self._dev, dtype=torch.int64).reshape(-1).contiguous()
-        elif env_ids is not None:  # a numpy array, a list, one int
-            ids = np.asarray(env_ids)
-            if ids.size and ids.dtype.kind not in "iu":
-                raise TypeError(f"env_ids must hold integers, got {ids.dtype}")
-            env_ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1), device=self._dev)
+        env_ids = self._env_ids_tensor(env_ids)
         w = self.dataset.map_width
         if self.array_backend != "numpy":
             return unpack_map_bits(self._map_bits, w, env_ids, dtype=dtype, wall=wall, out=out, err=self._t["err"])
@@ -586,6 +579,90 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             return res
         np.copyto(out, res.reshape(out.shape), casting="no")
         return out
+
+    def _env_ids_tensor(self, env_ids):
+        """`env_ids` (any integer tensor on any device, a numpy array, a list, one int; None stays None) as a
+        contiguous 1-d int64 tensor on the env's device."""
+        import torch
+
+        if env_ids is None:
+            return None
+        if isinstance(env_ids, torch.Tensor):
+            if env_ids.is_floating_point() or env_ids.is_complex() or env_ids.dtype == torch.bool:
+                raise TypeError(f"env_ids must hold integers, got {env_ids.dtype}")
+            return env_ids.to(device=self._dev, dtype=torch.int64).reshape(-1).contiguous()
+        ids = np.asarray(env_ids)
+        if ids.size and ids.dtype.kind not in "iu":
+            raise TypeError(f"env_ids must hold integers, got {ids.dtype}")
+        return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1), device=self._dev)
+
+    def _pose_query(self, poses, env_ids):
+        """Arguments of scan_poses / pose_scores: (bits [n_src, H, wpr], poses as a float32 [M, K, 2] device tensor,
+        map_ids or None, env_ids as a tensor or None).  A static-map env has one map, which every pose set uses; its
+        env_ids only choose the observed rows, and one outside [0, num_envs) is flagged like a map id."""
+        import torch
+
+        if self._closed:
+            raise RuntimeError("environment is closed")
+        ids = self._env_ids_tensor(env_ids)
+        h, w = self.dataset.map_height, self.dataset.map_width
+        p = torch.as_tensor(poses, dtype=torch.float32, device=self._dev).contiguous()
+        m = self.num_envs if ids is None else ids.shape[0]
+        if p.dim() != 3 or p.shape[2] != 2 or p.shape[0] != m:
+            raise ValueError(f"poses must have shape [{m}, K, 2] (one pose set per chosen sub-env), got "
+                             f"{tuple(p.shape)}")
+        bits = self._t["occ"].view(1 if self.static_map else self.num_envs, h, words_per_row(w))
+        if self.static_map and ids is not None and ids.numel():
+            bad = ((ids < 0) | (ids >= self.num_envs)).any().to(torch.int32) * N.APG_ERR_INDEX
+            self._t["err"].bitwise_or_(bad)
+        return bits, p, (None if self.static_map else ids), ids
+
+    def _pose_result(self, res, out):
+        """numpy backend: the device result as a numpy array (`out`, when given, filled and returned), errors raised
+        at once.  torch backend: the tensor itself (errors are raised lazily by check_errors())."""
+        if self.array_backend != "numpy":
+            return res
+        host = res.cpu().numpy()
+        self.check_errors(block=True)
+        if out is None:
+            return host
+        np.copyto(out, host.reshape(out.shape), casting="no")
+        return out
+
+    def scan_poses(self, poses, env_ids=None, *, normalize: bool = True, out=None):
+        """What the LIDAR would read from `poses` [M, K, 2] ((x, y) in cells, K poses per chosen sub-env) on the
+        current maps of the sub-envs `env_ids` (any order, duplicates allowed; None: every sub-env): float32
+        [M, K, beams], the env's exact scan (scan_poses.lidar_scan_poses on the env's occupancy rows, beam directions
+        and lidar_range) -- with normalize=True and the env's own position it equals obs["lidar"] bit for bit;
+        normalize=False gives distances in cells.  Works in both map_obs modes and for every map source.  A pose with
+        a non-finite coordinate yields NaN and raises ValueError, an env id outside [0, num_envs) scans an empty map
+        and raises IndexError, both through check_errors() (torch backend: lazily; numpy backend: at once).  The
+        numpy backend takes and returns numpy arrays; the torch backend returns device tensors (`out`: a contiguous
+        device tensor to write into)."""
+        bits, p, map_ids, _ = self._pose_query(poses, env_ids)
+        torch_out = out if self.array_backend != "numpy" else None
+        res = lidar_scan_poses(bits, self.dataset.map_width, p, map_ids, beams=self.lidar_beam_count,
+                               lidar_range=self.lidar_range, normalize=normalize, out=torch_out, err=self._t["err"],
+                               beam_dirs=self._t["beam_dirs"])
+        return self._pose_result(res, out)
+
+    def pose_scores(self, poses, observed=None, env_ids=None, *, out=None):
+        """Squared error [M, K] between the normalised scan of each of `poses` [M, K, 2] and `observed` [M, beams]
+        (None: the current obs["lidar"] rows of the chosen sub-envs), summed in float32 in beam order
+        (scan_poses.lidar_pose_scores): 0.0 exactly for a pose that reproduces the observation.  The scans are not
+        written to memory.  Arguments and errors as scan_poses()."""
+        import torch
+
+        bits, p, map_ids, ids = self._pose_query(poses, env_ids)
+        if observed is None:
+            lidar = self._t["lidar"]
+            observed = lidar if ids is None else lidar[ids.clamp(0, self.num_envs - 1)]
+        observed = torch.as_tensor(observed, dtype=torch.float32, device=self._dev).contiguous()
+        torch_out = out if self.array_backend != "numpy" else None
+        res = lidar_pose_scores(bits, self.dataset.map_width, p, observed, map_ids, beams=self.lidar_beam_count,
+                                lidar_range=self.lidar_range, out=torch_out, err=self._t["err"],
+                                beam_dirs=self._t["beam_dirs"])
+        return self._pose_result(res, out)
 
     def _launch_step(self, a_t, p_t):
         if self.use_torch_op:
@@ -621,7 +698,9 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         if bits & N.APG_ERR_PREFETCH:
             raise N.ApgError("an autoreset found no prefetched map (prefetch protocol violated)")
         if bits & N.APG_ERR_INDEX:
-            raise IndexError("unpack_maps(): an env id outside [0, num_envs)")
+            raise IndexError("unpack_maps() / scan_poses() / pose_scores(): an env id outside [0, num_envs)")
+        if bits & N.APG_ERR_BAD_POSE:
+            raise ValueError("scan_poses() / pose_scores(): a pose with a non-finite coordinate")
 
     def check_errors(self, block: bool = True):
         """Raise the reference's exception for any error flagged by the kernels so far."""

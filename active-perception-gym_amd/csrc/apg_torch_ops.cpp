@@ -11,6 +11,9 @@
 //   torch.ops.apgym.image_reset(ImageEnv env) -> ()
 //   torch.ops.apgym.image_step(ImageEnv env, Tensor action, Tensor prediction, int t, int prev_done) -> ()
 //   torch.ops.apgym.unpack_map_bits(Tensor bits, int width, Tensor? env_ids, Tensor out, float wall, Tensor? err) -> ()
+//   torch.ops.apgym.lidar_scan_poses(Tensor bits, int width, Tensor poses, Tensor? map_ids, Tensor beam_dirs,
+//                                    float lidar_range, bool normalize, Tensor? observed, Tensor? scan, Tensor? score,
+//                                    Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -23,6 +26,8 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -218,6 +223,66 @@ void unpack_map_bits(const at::Tensor &bits, int64_t width, const c10::optional<
         "apg_lidar_unpack_maps");
 }
 
+// Exact scans and fused scores at caller-chosen poses (apg_lidar_scan_poses).  bits: int64 [n_src, H, ceil(width / 64)];
+// poses: float32 [M, K, 2]; map_ids: int64 [M] or None; beam_dirs: float32 [B, 2]; observed: float32 [M, B] or None
+// (needed with score); scan: float32 [M, K, B] or None; score: float32 [M, K] or None; err: int32 [1] or None.
+void lidar_scan_poses(const at::Tensor &bits, int64_t width, const at::Tensor &poses,
+                      const c10::optional<at::Tensor> &map_ids, const at::Tensor &beam_dirs, double lidar_range,
+                      bool normalize, const c10::optional<at::Tensor> &observed, const c10::optional<at::Tensor> &scan,
+                      const c10::optional<at::Tensor> &score, const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(bits.is_cuda(), "bits must be on a GPU device, got ", bits.device());
+  const at::Device dev = bits.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(bits.scalar_type() == at::kLong && bits.dim() == 3 && bits.is_contiguous(),
+              "bits must be a contiguous int64 [n_src, H, ceil(width / 64)] tensor");
+  TORCH_CHECK(width >= 1 && width <= 511 && bits.size(2) == (width + 63) / 64, "bits has ", bits.size(2),
+              " words per row, width ", width, " needs ", (width + 63) / 64, " (width 1..511)");
+  TORCH_CHECK(poses.dim() == 3 && poses.size(2) == 2, "poses must be [M, K, 2]");
+  const int64_t m = poses.size(0), k = poses.size(1);
+  TORCH_CHECK(k <= INT32_MAX, "poses: too many poses per set");
+  check_io(poses, dev, 2 * m * k, "poses");
+  TORCH_CHECK(beam_dirs.dim() == 2 && beam_dirs.size(1) == 2, "beam_dirs must be [B, 2]");
+  const int64_t b = beam_dirs.size(0);
+  check_io(beam_dirs, dev, 2 * b, "beam_dirs");
+  apg_scan_poses_args a{};
+  a.occ = reinterpret_cast<const uint64_t *>(ptr(bits));
+  a.poses = reinterpret_cast<const float *>(ptr(poses));
+  a.beam_dirs = reinterpret_cast<const float *>(ptr(beam_dirs));
+  if (map_ids.has_value() && map_ids->defined()) {
+    TORCH_CHECK(map_ids->device() == dev && map_ids->scalar_type() == at::kLong && map_ids->dim() == 1 &&
+                    map_ids->is_contiguous() && map_ids->numel() == m,
+                "map_ids must be a contiguous int64 [M] tensor on ", dev);
+    a.map_ids = reinterpret_cast<const int64_t *>(ptr(*map_ids));
+  }
+  if (observed.has_value() && observed->defined()) {
+    check_io(*observed, dev, m * b, "observed");
+    a.observed = reinterpret_cast<const float *>(ptr(*observed));
+  }
+  if (scan.has_value() && scan->defined()) {
+    check_io(*scan, dev, m * k * b, "scan");
+    a.scan = reinterpret_cast<float *>(ptr(*scan));
+  }
+  if (score.has_value() && score->defined()) {
+    check_io(*score, dev, m * k, "score");
+    TORCH_CHECK(a.observed || m * b == 0, "score needs observed");
+    a.score = reinterpret_cast<float *>(ptr(*score));
+  }
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    a.err = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  a.n_src = bits.size(0);
+  a.m = m;
+  a.height = (int32_t)bits.size(1);
+  a.width = (int32_t)width;
+  a.k = (int32_t)k;
+  a.beams = (int32_t)std::min<int64_t>(b, INT32_MAX);
+  a.normalize = normalize ? 1 : 0;
+  a.lidar_range = (float)lidar_range;
+  check(apg_lidar_scan_poses(&a, stream_of(dev)), "apg_lidar_scan_poses");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -234,4 +299,7 @@ TORCH_LIBRARY(apgym, m) {
   m.def("unpack_map_bits(Tensor bits, int width, Tensor? env_ids, Tensor(a!) out, float wall, Tensor(b!)? err=None) "
         "-> ()",
         unpack_map_bits);
+  m.def("lidar_scan_poses(Tensor bits, int width, Tensor poses, Tensor? map_ids, Tensor beam_dirs, float lidar_range, "
+        "bool normalize, Tensor? observed, Tensor(a!)? scan, Tensor(b!)? score, Tensor(c!)? err) -> ()",
+        lidar_scan_poses);
 }

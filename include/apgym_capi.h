@@ -19,8 +19,9 @@
  *   apg_map_generate
  *       FloorMapDatasetRooms.get_data_point  ap_gym/envs/floor_map/floor_map_dataset_rooms.py:25-89
  *       FloorMapDatasetMaze.get_data_point   ap_gym/envs/floor_map/floor_map_dataset_maze.py:24-55
- *   apg_lidar_scan_batch
- *       LIDARLocalization2DEnv.__lidar_scan  ap_gym/envs/lidar_localization2d.py:496-536
+ *   apg_lidar_scan_batch / apg_lidar_scan_poses
+ *       LIDARLocalization2DEnv.__lidar_scan  ap_gym/envs/lidar_localization2d.py:496-536 (scan_poses: over the beams
+ *       of __get_obs :238-277, at poses the caller chooses)
  *   apg_lidar_render_track
  *       the render-only state of LIDARLocalization2DEnv (observation_map, trajectory, last readings)
  *       ap_gym/envs/lidar_localization2d.py:239-261, 312-313, 326-327, 377-380 used by render() :391-494.
@@ -80,7 +81,9 @@ extern "C" {
 #define APG_ERR_PREFETCH 32u      /* a maze autoreset found no prefetched map (prefetch protocol violated) */
 #define APG_ERR_NO_FREE_CELL 64u  /* a pool map without a free cell was drawn: numpy's integers(0, 0) raises
                                      ValueError("high <= 0") in reset (lidar_localization2d.py:302-303) */
-#define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps: a map id outside [0, n_src) (raised as IndexError) */
+#define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps / apg_lidar_scan_poses: a map id outside [0, n_src) (raised
+                                     as IndexError) */
+#define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses: a pose with a non-finite coordinate (raised as ValueError) */
 
 #define APG_MAP_ROOMS 0
 #define APG_MAP_MAZE 1
@@ -283,6 +286,37 @@ int apg_lidar_scan_batch(const uint64_t *occ, const int32_t *map_index, int h, i
 #define APG_UNPACK_U8 3
 int apg_lidar_unpack_maps(const uint64_t *occ, int64_t n_src, int height, int width, const int64_t *env_ids,
                           int64_t count, int dtype, float wall, void *dst, uint32_t *err, apg_stream_t stream);
+
+/* Exact LIDAR scans, and their fused squared-error scores, at caller-chosen poses (an addition to ABI 0.4; no changes
+ * to existing structs).  For each pose set i of m: k poses (x, y), scanned against map map_ids[i] of occ (the packed
+ * layout above; the padding bits at x >= width are ignored) with the `beams` directions of beam_dirs.  Beam b of pose p
+ * is the segment p -> p + beam_dirs[b] (one f32 add per coordinate), scanned exactly as the env's observation is
+ * (csrc/apg_scan.hpp).
+ *   scan[i][p][b]   normalize != 0: the observation's value, clip(d / lidar_range, -1, 1) in f32; else the distance d
+ *                   in cells
+ *   score[i][p]     sum over b, in beam order from 0, of (s_b - observed[i][b])^2 with s the NORMALISED scan, every
+ *                   operation rounded to f32 on its own (a NaN in observed gives a NaN score: not an error)
+ * Either output may be NULL (not both).  Limits: height and width 1..511, 0 < lidar_range <= 60, beams 1..4096.
+ * Pose domain: a pose with a non-finite coordinate is never scanned: its scan values and score are NaN and
+ * APG_ERR_BAD_POSE is OR-ed into *err (so is a beam direction with a non-finite component or one beyond 60 cells: its
+ * values are NaN).  A finite pose outside [-64, width + 64] x [-64, height + 64] is not walked either: no beam
+ * reaches a map cell from there, so every beam reads |q - p|, what the walk returns for an empty segment; that is not
+ * an error.  A map id outside [0, n_src) is never read: its pose set is scanned against an all-zero map and
+ * APG_ERR_INDEX is set.  map_ids NULL needs n_src == 1 or m <= n_src.  m == 0 or k == 0 launches nothing. */
+typedef struct apg_scan_poses_args {
+  const uint64_t *occ;      /* [n_src][height][ceil(width/64)], layout of apg_lidar_state.occ */
+  const int64_t *map_ids;   /* [m] or NULL: map i, or map 0 for every set when n_src == 1 */
+  const float *poses;       /* [m][k][2] (x, y) in cells, the convention of apg_lidar_state.pos */
+  const float *beam_dirs;   /* [beams][2], each no longer than lidar_range */
+  const float *observed;    /* [m][beams] or NULL (required with score) */
+  float *scan;              /* [m][k][beams] or NULL */
+  float *score;             /* [m][k] or NULL */
+  uint32_t *err;            /* or NULL */
+  int64_t n_src, m;
+  int32_t height, width, k, beams, normalize;
+  float lidar_range;
+} apg_scan_poses_args;
+int apg_lidar_scan_poses(const apg_scan_poses_args *args, apg_stream_t stream);
 
 /* ---------------------------------------------------------------- LIDAR render path (not the hot path)
  * Render-only state of the tracked sub-envs: what LIDARLocalization2DEnv keeps for render()
