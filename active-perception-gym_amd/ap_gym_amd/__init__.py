@@ -37,6 +37,7 @@ from .loss_fn import (  # noqa: F401
     ZeroLossFn,
 )
 from .map_bits import unpack_map_bits  # noqa: F401
+from .move_poses import MovePosesResult, lidar_move_poses  # noqa: F401
 from .scan_poses import lidar_pose_scores, lidar_scan_poses  # noqa: F401
 from .registration import make_vec, register, registry  # noqa: F401
 from .spaces import ActivePerceptionActionSpace, ImageSpace, LogitSpace  # noqa: F401

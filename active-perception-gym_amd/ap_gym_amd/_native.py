@@ -30,13 +30,21 @@ APG_ERR_OOB_Y = 8
 APG_ERR_OOB_X = 16
 APG_ERR_PREFETCH = 32
 APG_ERR_NO_FREE_CELL = 64
-APG_ERR_INDEX = 128  # apg_lidar_unpack_maps / apg_lidar_scan_poses: a map id outside [0, n_src) (raised as IndexError)
-APG_ERR_BAD_POSE = 256  # apg_lidar_scan_poses: a pose with a non-finite coordinate (raised as ValueError)
+APG_ERR_INDEX = 128  # unpack_maps / scan_poses / move_poses: a map id outside [0, n_src) (raised as IndexError)
+APG_ERR_BAD_POSE = 256  # scan_poses / move_poses: a pose or candidate action with a non-finite coordinate (ValueError)
 # k_scan_poses' work split (csrc/apg_scan_poses.hip SP_TILE, SP_MAX_MPW, SP_MAX_GRID): rays per workgroup pass, pose
 # sets a workgroup takes at once when a set is small, workgroups per launch
 SCAN_POSES_TILE = 256
 SCAN_POSES_MAX_MPW = 32
 SCAN_POSES_MAX_GRID = 8192
+# k_move_poses' work split (csrc/apg_move_poses.hip MP_TILE, MP_MAX_MPW, MP_MAX_GRID, MP_MAX_T): candidates per
+# workgroup item (sets of at most MOVE_POSES_SMALL_K = tile / 2 candidates share a workgroup), sets per item,
+# workgroups per launch, actions per candidate
+MOVE_POSES_TILE = 256
+MOVE_POSES_SMALL_K = MOVE_POSES_TILE // 2
+MOVE_POSES_MAX_MPW = 32
+MOVE_POSES_MAX_GRID = 8192
+MOVE_POSES_MAX_T = 4096
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -105,6 +113,13 @@ class ScanPosesArgs(ctypes.Structure):
         ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
         (n, ctypes.c_int32) for n in ("height", "width", "k", "beams", "normalize")] + [
         ("lidar_range", ctypes.c_float)]
+
+
+class MovePosesArgs(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("occ", "map_ids", "poses", "actions", "max_steps", "origin", "origin_alias", "pos",
+                                   "steps", "terminated", "base_reward", "odometry", "err")] + [
+        ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ("height", "width", "k", "t")]
 
 
 class LidarSizes(ctypes.Structure):
@@ -190,6 +205,7 @@ SYMBOLS = [
     ("apg_lidar_unpack_maps", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_float, _vp, _vp, _vp]),
     ("apg_lidar_scan_poses", ctypes.c_int, [ctypes.POINTER(ScanPosesArgs), _vp]),
+    ("apg_lidar_move_poses", ctypes.c_int, [ctypes.POINTER(MovePosesArgs), _vp]),
     ("apg_lidar_render_track", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp,
                                               ctypes.POINTER(LidarOutputs), ctypes.POINTER(LidarRenderState), _vp]),
     ("apg_rng_draws", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -64,6 +64,7 @@ from . import _native as N
 from .floor_map import FloorMapDataset, FloorMapDatasetMaze, FloorMapDatasetRooms, as_floor_map_dataset
 from .loss_fn import WeightedLossFn, affine_f32, regression_loss
 from .map_bits import host_words_np, unpack_map_bits, words_per_row
+from .move_poses import lidar_move_poses
 from .scan_poses import lidar_pose_scores, lidar_scan_poses
 from .spaces import ActivePerceptionActionSpace, Box, Dict, ImageSpace, batch_space
 from .vector_env import VectorEnv
@@ -664,6 +665,75 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
                                 beam_dirs=self._t["beam_dirs"])
         return self._pose_result(res, out)
 
+    def lookahead(self, actions, env_ids=None, *, scans="last"):
+        """Where would these actions take the agent, and what would it observe?  `actions` [M, K, T, 2] (or [M, K, 2]
+        for T = 1): K candidate sequences of T actions for each of the sub-envs `env_ids` (any order, duplicates
+        allowed; None: every sub-env), rolled out open-loop from the sub-env's current position on its current map
+        with the env's own movement (move_poses.lidar_move_poses on the env's occupancy rows), bit for bit what
+        step() does -- and without touching the env: no position, flag, RNG, elapsed count or output buffer changes.
+        A candidate terminates when it leaves the map or reaches the sub-env's step limit (max_steps = step limit -
+        elapsed steps); the odometry is taken against the episode's origin, including the reference's quirk during
+        an episode's first step.  Returns a dict:
+
+          pos            [M, K, T, 2] the pose after each action; after the terminating action the final pose repeats
+          steps          int32 [M, K] the actions applied: the terminating one's number, or T
+          terminated     bool [M, K]
+          base_reward    [M, K, T], 0 after termination
+          odometry       [M, K, T, 2] obs["odometry"] after each action, repeated after termination
+          lidar          obs["lidar"] at the poses: scans="last" [M, K, beams] at pos[:, :, -1]; scans="all"
+                         [M, K, T, beams]; scans=None: absent (scan_poses.lidar_scan_poses on `pos`)
+          pending_reset  bool [M]: the sub-env's episode is over and its next step() autoresets.  Its rollout starts
+                         from the finished episode's final pose on its old map (what the env still holds), with no
+                         step limit when the episode ended by it; step() will not continue from there.
+
+        Works in both map_obs modes and for every map source.  A non-finite action gives NaN from that action on and
+        raises ValueError, an env id outside [0, num_envs) moves on an empty map and raises IndexError, both through
+        check_errors() (torch backend: lazily; numpy backend: at once).  The numpy backend takes and returns numpy
+        arrays; the torch backend returns device tensors."""
+        import torch
+
+        if self._closed:
+            raise RuntimeError("environment is closed")
+        if scans not in ("last", "all", None):
+            raise ValueError(f"scans must be 'last', 'all' or None, got {scans!r}")
+        a = torch.as_tensor(actions, dtype=torch.float32, device=self._dev)
+        if a.dim() == 3:
+            a = a.unsqueeze(2)
+        if a.dim() != 4 or a.shape[3] != 2:
+            raise ValueError(f"actions must have shape [M, K, T, 2] or [M, K, 2], got {tuple(a.shape)}")
+        a = a.contiguous()
+        m, k, t = a.shape[0], a.shape[1], a.shape[2]
+        n, T = self.num_envs, self._t
+        ids = self._env_ids_tensor(env_ids)
+        if m != (n if ids is None else ids.shape[0]):
+            raise ValueError(f"actions must have one candidate set per chosen sub-env "
+                             f"({n if ids is None else ids.shape[0]}), got {m}")
+        pos0, origin, elapsed, flags = T["pos"], T["init_pos"], T["elapsed"], T["flags"]
+        if ids is not None:  # (an id out of range is flagged by the kernel or _pose_query; here it only must not fault)
+            safe = ids.clamp(0, n - 1)
+            pos0, origin, elapsed, flags = pos0[safe], origin[safe], elapsed[safe], flags[safe]
+        start = pos0[:, None, :].expand(m, k, 2).contiguous()
+        bits, start, map_ids, _ = self._pose_query(start, ids)
+        max_steps = (self.max_episode_steps - elapsed).to(torch.int32).contiguous()
+        alias = (flags & 4).ne(0).to(torch.uint8)  # F_FIRST of the step kernel
+        w, err = self.dataset.map_width, T["err"]
+        res = lidar_move_poses(bits, w, start, a, map_ids, max_steps=max_steps, origin=origin.contiguous(),
+                               origin_alias=alias, err=err)
+        out = dict(pos=res.pos, steps=res.steps, terminated=res.terminated.bool(), base_reward=res.base_reward,
+                   odometry=res.odometry)
+        if scans is not None:
+            at = res.pos if scans == "all" else res.pos[:, :, -1:, :]
+            lidar = lidar_scan_poses(bits, w, at.reshape(m, k * at.shape[2], 2).contiguous(), map_ids,
+                                     beams=self.lidar_beam_count, lidar_range=self.lidar_range, err=err,
+                                     beam_dirs=T["beam_dirs"])
+            out["lidar"] = lidar.view((m, k, t, -1) if scans == "all" else (m, k, -1))
+        out["pending_reset"] = (flags & 1).ne(0)  # F_AUTORESET
+        if self.array_backend != "numpy":
+            return out
+        out = {name: v.cpu().numpy() for name, v in out.items()}
+        self.check_errors(block=True)
+        return out
+
     def _launch_step(self, a_t, p_t):
         if self.use_torch_op:
             self._step_op(self._h, a_t, p_t)
@@ -698,9 +768,11 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         if bits & N.APG_ERR_PREFETCH:
             raise N.ApgError("an autoreset found no prefetched map (prefetch protocol violated)")
         if bits & N.APG_ERR_INDEX:
-            raise IndexError("unpack_maps() / scan_poses() / pose_scores(): an env id outside [0, num_envs)")
+            raise IndexError("unpack_maps() / scan_poses() / pose_scores(): an env id outside [0, num_envs)"
+                             " (lookahead() too)")
         if bits & N.APG_ERR_BAD_POSE:
-            raise ValueError("scan_poses() / pose_scores(): a pose with a non-finite coordinate")
+            raise ValueError("scan_poses() / pose_scores(): a pose with a non-finite coordinate"
+                             " (lookahead(): a non-finite action)")
 
     def check_errors(self, block: bool = True):
         """Raise the reference's exception for any error flagged by the kernels so far."""

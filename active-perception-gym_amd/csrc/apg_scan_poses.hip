@@ -3,8 +3,8 @@
 // For each pose set m of M: K poses, one packed map (map_ids[m] of an apg_lidar_state.occ-layout batch) and B beam
 // directions.  Beam b of pose p is the segment p -> p + dir[b] (one f32 add per coordinate, as the step kernel and
 // the reference's __get_obs build it), scanned with apg::lidar_scan of apg_scan.hpp unchanged -- the scan the env's
-// observation is made of, bit for bit -- through the row source RowsLds below.  Outputs (either may be absent):
-// scan[M][K][B] (normalised like the observation, or the distance in cells) and score[M][K], the squared error of the
+// observation is made of, bit for bit -- through the row source RowsLds (apg_rows_lds.hpp).  Outputs (either may be
+// absent): scan[M][K][B] (normalised like the observation, or the distance in cells) and score[M][K], the squared error of the
 // pose's normalised scan against observed[M][B], accumulated in f32 in beam order.
 //
 // Work assignment.  A ray is (pose, beam); rays are numbered beam-minor (pose = r / B, beam = r % B), so a wave's
@@ -31,6 +31,7 @@
 
 #include "../../include/apgym_capi.h"
 #include "apg_host.hpp"
+#include "apg_rows_lds.hpp"
 #include "apg_scan.hpp"
 
 namespace apg {
@@ -61,24 +62,6 @@ struct ScanPosesArgs {
   int32_t h, w, k, beams, normalize;
   int32_t mpw, ppt, tps;  // sets per item, poses per tile, tiles per set (1 when mpw > 1)
   float range;
-};
-
-// Bit rows staged in LDS ([h][wpr], padding bits cleared), read through a 64-column window at x0 as RowsGlobal reads
-// global memory: zero outside the map, so segments that leave it need no special case.
-struct RowsLds {
-  typedef uint64_t word;
-  const uint64_t *rows;
-  int h, wpr, x0;
-  APG_DEV uint64_t row(int y) const {
-    if ((unsigned)y >= (unsigned)h) return 0ULL;
-    return extract_window_row64(rows + y * wpr, wpr, x0);
-  }
-  APG_DEV uint64_t row_nw(int y) const { return row(y); }
-  APG_DEV uint64_t or_rows(int j0, int j1, int) const {
-    uint64_t acc = 0ULL;
-    for (int j = j0; j <= j1; j++) acc |= row(j);
-    return acc;
-  }
 };
 
 __global__ __launch_bounds__(SP_TILE, SP_MIN_WAVES) void k_scan_poses(ScanPosesArgs A) {

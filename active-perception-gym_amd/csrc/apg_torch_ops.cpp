@@ -14,6 +14,9 @@
 //   torch.ops.apgym.lidar_scan_poses(Tensor bits, int width, Tensor poses, Tensor? map_ids, Tensor beam_dirs,
 //                                    float lidar_range, bool normalize, Tensor? observed, Tensor? scan, Tensor? score,
 //                                    Tensor? err) -> ()
+//   torch.ops.apgym.lidar_move_poses(Tensor bits, int width, Tensor poses, Tensor actions, Tensor? map_ids,
+//                                    Tensor? max_steps, Tensor? origin, Tensor? origin_alias, Tensor pos, Tensor steps,
+//                                    Tensor terminated, Tensor? base_reward, Tensor? odometry, Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -283,6 +286,89 @@ void lidar_scan_poses(const at::Tensor &bits, int64_t width, const at::Tensor &p
   check(apg_lidar_scan_poses(&a, stream_of(dev)), "apg_lidar_scan_poses");
 }
 
+// Open-loop rollouts of candidate actions from caller-chosen poses (apg_lidar_move_poses).  bits: int64
+// [n_src, H, ceil(width / 64)]; poses: float32 [M, K, 2]; actions: float32 [M, K, T, 2]; map_ids: int64 [M] or None;
+// max_steps: int32 [M] or None; origin: float32 [M, 2] or None; origin_alias: uint8 [M] or None; pos: float32
+// [M, K, T, 2]; steps: int32 [M, K]; terminated: uint8 [M, K]; base_reward: float32 [M, K, T] or None; odometry:
+// float32 [M, K, T, 2] or None (needs origin); err: int32 [1] or None.
+void lidar_move_poses(const at::Tensor &bits, int64_t width, const at::Tensor &poses, const at::Tensor &actions,
+                      const c10::optional<at::Tensor> &map_ids, const c10::optional<at::Tensor> &max_steps,
+                      const c10::optional<at::Tensor> &origin, const c10::optional<at::Tensor> &origin_alias,
+                      at::Tensor pos, at::Tensor steps, at::Tensor terminated,
+                      const c10::optional<at::Tensor> &base_reward, const c10::optional<at::Tensor> &odometry,
+                      const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(bits.is_cuda(), "bits must be on a GPU device, got ", bits.device());
+  const at::Device dev = bits.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(bits.scalar_type() == at::kLong && bits.dim() == 3 && bits.is_contiguous(),
+              "bits must be a contiguous int64 [n_src, H, ceil(width / 64)] tensor");
+  TORCH_CHECK(width >= 1 && width <= 511 && bits.size(2) == (width + 63) / 64, "bits has ", bits.size(2),
+              " words per row, width ", width, " needs ", (width + 63) / 64, " (width 1..511)");
+  TORCH_CHECK(poses.dim() == 3 && poses.size(2) == 2, "poses must be [M, K, 2]");
+  const int64_t m = poses.size(0), k = poses.size(1);
+  TORCH_CHECK(k <= INT32_MAX, "poses: too many candidates per set");
+  check_io(poses, dev, 2 * m * k, "poses");
+  TORCH_CHECK(actions.dim() == 4 && actions.size(0) == m && actions.size(1) == k && actions.size(3) == 2,
+              "actions must be [M, K, T, 2]");
+  const int64_t t = actions.size(2);
+  TORCH_CHECK(t >= 1 && t <= 4096, "actions: T must be in [1, 4096], got ", t);
+  check_io(actions, dev, 2 * m * k * t, "actions");
+  auto typed = [&](const at::Tensor &x, at::ScalarType st, int64_t numel, const char *name) {
+    TORCH_CHECK(x.device() == dev && x.scalar_type() == st && x.is_contiguous() && x.numel() == numel, name,
+                " must be a contiguous ", st, " tensor of ", numel, " elements on ", dev);
+  };
+  apg_move_poses_args a{};
+  a.occ = reinterpret_cast<const uint64_t *>(ptr(bits));
+  a.poses = reinterpret_cast<const float *>(ptr(poses));
+  a.actions = reinterpret_cast<const float *>(ptr(actions));
+  if (map_ids.has_value() && map_ids->defined()) {
+    TORCH_CHECK(map_ids->dim() == 1, "map_ids must be 1-d");
+    typed(*map_ids, at::kLong, m, "map_ids");
+    a.map_ids = reinterpret_cast<const int64_t *>(ptr(*map_ids));
+  }
+  if (max_steps.has_value() && max_steps->defined()) {
+    typed(*max_steps, at::kInt, m, "max_steps");
+    a.max_steps = reinterpret_cast<const int32_t *>(ptr(*max_steps));
+  }
+  const bool has_origin = origin.has_value() && origin->defined();
+  if (has_origin) {
+    check_io(*origin, dev, 2 * m, "origin");
+    a.origin = reinterpret_cast<const float *>(ptr(*origin));
+  }
+  if (origin_alias.has_value() && origin_alias->defined()) {
+    TORCH_CHECK(has_origin, "origin_alias needs origin");
+    typed(*origin_alias, at::kByte, m, "origin_alias");
+    a.origin_alias = reinterpret_cast<const uint8_t *>(ptr(*origin_alias));
+  }
+  check_io(pos, dev, 2 * m * k * t, "pos");
+  typed(steps, at::kInt, m * k, "steps");
+  typed(terminated, at::kByte, m * k, "terminated");
+  a.pos = reinterpret_cast<float *>(ptr(pos));
+  a.steps = reinterpret_cast<int32_t *>(ptr(steps));
+  a.terminated = reinterpret_cast<uint8_t *>(ptr(terminated));
+  if (base_reward.has_value() && base_reward->defined()) {
+    check_io(*base_reward, dev, m * k * t, "base_reward");
+    a.base_reward = reinterpret_cast<float *>(ptr(*base_reward));
+  }
+  if (odometry.has_value() && odometry->defined()) {
+    TORCH_CHECK(has_origin, "odometry needs origin");
+    check_io(*odometry, dev, 2 * m * k * t, "odometry");
+    a.odometry = reinterpret_cast<float *>(ptr(*odometry));
+  }
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    a.err = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  a.n_src = bits.size(0);
+  a.m = m;
+  a.height = (int32_t)bits.size(1);
+  a.width = (int32_t)width;
+  a.k = (int32_t)k;
+  a.t = (int32_t)t;
+  check(apg_lidar_move_poses(&a, stream_of(dev)), "apg_lidar_move_poses");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -302,4 +388,8 @@ TORCH_LIBRARY(apgym, m) {
   m.def("lidar_scan_poses(Tensor bits, int width, Tensor poses, Tensor? map_ids, Tensor beam_dirs, float lidar_range, "
         "bool normalize, Tensor? observed, Tensor(a!)? scan, Tensor(b!)? score, Tensor(c!)? err) -> ()",
         lidar_scan_poses);
+  m.def("lidar_move_poses(Tensor bits, int width, Tensor poses, Tensor actions, Tensor? map_ids, Tensor? max_steps, "
+        "Tensor? origin, Tensor? origin_alias, Tensor(a!) pos, Tensor(b!) steps, Tensor(c!) terminated, "
+        "Tensor(d!)? base_reward, Tensor(e!)? odometry, Tensor(f!)? err) -> ()",
+        lidar_move_poses);
 }

@@ -22,6 +22,9 @@
  *   apg_lidar_scan_batch / apg_lidar_scan_poses
  *       LIDARLocalization2DEnv.__lidar_scan  ap_gym/envs/lidar_localization2d.py:496-536 (scan_poses: over the beams
  *       of __get_obs :238-277, at poses the caller chooses)
+ *   apg_lidar_move_poses
+ *       the movement of LIDARLocalization2DEnv._step  ap_gym/envs/lidar_localization2d.py:330-375 and TimeLimit's
+ *       termination, for candidate actions from poses the caller chooses (no env state is advanced)
  *   apg_lidar_render_track
  *       the render-only state of LIDARLocalization2DEnv (observation_map, trajectory, last readings)
  *       ap_gym/envs/lidar_localization2d.py:239-261, 312-313, 326-327, 377-380 used by render() :391-494.
@@ -81,9 +84,10 @@ extern "C" {
 #define APG_ERR_PREFETCH 32u      /* a maze autoreset found no prefetched map (prefetch protocol violated) */
 #define APG_ERR_NO_FREE_CELL 64u  /* a pool map without a free cell was drawn: numpy's integers(0, 0) raises
                                      ValueError("high <= 0") in reset (lidar_localization2d.py:302-303) */
-#define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps / apg_lidar_scan_poses: a map id outside [0, n_src) (raised
-                                     as IndexError) */
-#define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses: a pose with a non-finite coordinate (raised as ValueError) */
+#define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps / apg_lidar_scan_poses / apg_lidar_move_poses: a map id
+                                     outside [0, n_src) (raised as IndexError) */
+#define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses / apg_lidar_move_poses: a pose (or a candidate action) with a
+                                     non-finite coordinate (raised as ValueError) */
 
 #define APG_MAP_ROOMS 0
 #define APG_MAP_MAZE 1
@@ -317,6 +321,49 @@ typedef struct apg_scan_poses_args {
   float lidar_range;
 } apg_scan_poses_args;
 int apg_lidar_scan_poses(const apg_scan_poses_args *args, apg_stream_t stream);
+
+/* Exact open-loop rollouts of candidate actions from caller-chosen poses (an addition to ABI 0.4; no changes to
+ * existing structs).  For each candidate set i of m: k start poses (x, y) and k sequences of t actions, moved on map
+ * map_ids[i] of occ (the packed layout above; the padding bits at x >= width are ignored).  One action applied to a
+ * pose is LIDARLocalization2DEnv.step's movement (lidar_localization2d.py:330-375) in the float32 operation order of
+ * apg_lidar_step: base_reward = 0.1 - 0.001 (ax^2 + ay^2); the action clamped to unit length when longer; one exact
+ * scan (csrc/apg_scan.hpp) to the target and the advance by its distance; when more than 1e-5 remains, the slide
+ * along the components of the remaining vector that are > 1e-5 (two axis scans, the first candidate when its distance
+ * is > 0, else the second); left = x < 0 || y < 0 || x >= width || y >= height before the clip to
+ * [0, width] x [0, height].  A candidate terminates at the first action n (1-based) after which it has left the map or
+ * n >= max_steps[i] (TimeLimit with issue_termination; max_steps NULL or <= 0: no limit).
+ *   pos[i][c][n]          the pose after action n; entries after the terminating action repeat the final pose
+ *   steps[i][c]           the number of actions applied: the terminating n, or t
+ *   terminated[i][c]      1 when the candidate terminated within its t actions
+ *   base_reward[i][c][n]  0 after termination
+ *   odometry[i][c][n]     the observation's normalised odometry of pos against origin[i]; where origin_alias[i] != 0
+ *                         the origin of every candidate of the set is that candidate's own pose after its first action,
+ *                         before the clip (the reference's initial_pos aliases pos during an episode's first step);
+ *                         repeated after termination
+ * Limits: height and width 1..511, t 1..4096.  Domain: a candidate with a non-finite start pose or action is not
+ * moved from that action on: its pos, base_reward and odometry are NaN from there, steps counts the valid actions
+ * before it, terminated is 0 and APG_ERR_BAD_POSE is OR-ed into *err.  A finite start pose outside the map is legal
+ * (its first action terminates it); scans that start more than 64 cells outside the map read the empty value.  A map
+ * id outside [0, n_src) is never read: its set moves on an all-zero map and APG_ERR_INDEX is set.  map_ids NULL needs
+ * n_src == 1 or m <= n_src.  m == 0 or k == 0 launches nothing. */
+typedef struct apg_move_poses_args {
+  const uint64_t *occ;          /* [n_src][height][ceil(width/64)], layout of apg_lidar_state.occ */
+  const int64_t *map_ids;       /* [m] or NULL: map i, or map 0 for every set when n_src == 1 */
+  const float *poses;           /* [m][k][2] start poses (x, y) in cells */
+  const float *actions;         /* [m][k][t][2] */
+  const int32_t *max_steps;     /* [m] or NULL */
+  const float *origin;          /* [m][2] or NULL (required with odometry and origin_alias) */
+  const uint8_t *origin_alias;  /* [m] or NULL */
+  float *pos;                   /* [m][k][t][2] */
+  int32_t *steps;               /* [m][k] */
+  uint8_t *terminated;          /* [m][k] */
+  float *base_reward;           /* [m][k][t] or NULL */
+  float *odometry;              /* [m][k][t][2] or NULL */
+  uint32_t *err;                /* or NULL */
+  int64_t n_src, m;
+  int32_t height, width, k, t;
+} apg_move_poses_args;
+int apg_lidar_move_poses(const apg_move_poses_args *args, apg_stream_t stream);
 
 /* ---------------------------------------------------------------- LIDAR render path (not the hot path)
  * Render-only state of the tracked sub-envs: what LIDARLocalization2DEnv keeps for render()
