@@ -32,6 +32,7 @@ APG_ERR_PREFETCH = 32
 APG_ERR_NO_FREE_CELL = 64
 APG_ERR_INDEX = 128  # unpack_maps / scan_poses / move_poses: a map id outside [0, n_src) (raised as IndexError)
 APG_ERR_BAD_POSE = 256  # scan_poses / move_poses: a pose or candidate action with a non-finite coordinate (ValueError)
+#                         pf_resample: a particle with such a pose, or with a NaN or +inf log-weight
 # k_scan_poses' work split (csrc/apg_scan_poses.hip SP_TILE, SP_MAX_MPW, SP_MAX_GRID): rays per workgroup pass, pose
 # sets a workgroup takes at once when a set is small, workgroups per launch
 SCAN_POSES_TILE = 256
@@ -45,6 +46,14 @@ MOVE_POSES_SMALL_K = MOVE_POSES_TILE // 2
 MOVE_POSES_MAX_MPW = 32
 MOVE_POSES_MAX_GRID = 8192
 MOVE_POSES_MAX_T = 4096
+# k_pf_resample's work split (csrc/apg_pf_resample.hip PF_WAVE_K, PF_TILE, PF_MAX_K, PF_MAX_GRID): sets of at most
+# PF_RESAMPLE_WAVE_K particles take one wave each, PF_RESAMPLE_SETS_PER_WG of them per workgroup of PF_RESAMPLE_TILE
+# threads; larger sets take one workgroup each; workgroups per launch
+PF_RESAMPLE_WAVE_K = 64
+PF_RESAMPLE_TILE = 256
+PF_RESAMPLE_SETS_PER_WG = PF_RESAMPLE_TILE // 64
+PF_RESAMPLE_MAX_K = 4096
+PF_RESAMPLE_MAX_GRID = 65536
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -120,6 +129,12 @@ class MovePosesArgs(ctypes.Structure):
                                    "steps", "terminated", "base_reward", "odometry", "err")] + [
         ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
         (n, ctypes.c_int32) for n in ("height", "width", "k", "t")]
+
+
+class PfResampleArgs(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("logw", "score", "poses", "u", "weight", "estimate", "ess", "index", "poses_out",
+                                   "logw_out", "resampled", "err")] + [
+        ("m", ctypes.c_int64), ("k", ctypes.c_int32), ("score_scale", ctypes.c_float), ("ess_frac", ctypes.c_float)]
 
 
 class LidarSizes(ctypes.Structure):
@@ -206,6 +221,7 @@ SYMBOLS = [
                                              ctypes.c_int, ctypes.c_float, _vp, _vp, _vp]),
     ("apg_lidar_scan_poses", ctypes.c_int, [ctypes.POINTER(ScanPosesArgs), _vp]),
     ("apg_lidar_move_poses", ctypes.c_int, [ctypes.POINTER(MovePosesArgs), _vp]),
+    ("apg_lidar_pf_resample", ctypes.c_int, [ctypes.POINTER(PfResampleArgs), _vp]),
     ("apg_lidar_render_track", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp,
                                               ctypes.POINTER(LidarOutputs), ctypes.POINTER(LidarRenderState), _vp]),
     ("apg_rng_draws", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -65,6 +65,7 @@ from .floor_map import FloorMapDataset, FloorMapDatasetMaze, FloorMapDatasetRoom
 from .loss_fn import WeightedLossFn, affine_f32, regression_loss
 from .map_bits import host_words_np, unpack_map_bits, words_per_row
 from .move_poses import lidar_move_poses
+from .pf_resample import PfUpdateResult, lidar_pf_resample
 from .scan_poses import lidar_pose_scores, lidar_scan_poses
 from .spaces import ActivePerceptionActionSpace, Box, Dict, ImageSpace, batch_space
 from .vector_env import VectorEnv
@@ -734,6 +735,40 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         self.check_errors(block=True)
         return out
 
+    def pf_update(self, particles, logw=None, *, sigma: float, env_ids=None, ess_frac: float = 0.5, u=None):
+        """The measurement update and resampling of a particle filter in two launches: pose_scores() of `particles`
+        [M, K, 2] ((x, y) in cells, K particles for each of the sub-envs `env_ids`; None: every sub-env) against the
+        sub-envs' current obs["lidar"], then pf_resample.lidar_pf_resample with the Gaussian likelihood
+        score_scale = float32(1 / (2 sigma^2)) on the log-weights `logw` [M, K] (None: all 0).  Sets whose effective
+        sample size fell below `ess_frac * K` are resampled with `u` [M] (None: drawn with torch.rand on the device).
+        Returns a PfUpdateResult: lidar_pf_resample's weight, estimate (in cells), ess, index, poses, logw and
+        resampled, plus `scores` [M, K].  A particle with a non-finite coordinate or a NaN / +inf log-weight has
+        weight 0, is never selected and raises ValueError, an env id outside [0, num_envs) IndexError, both through
+        check_errors() (torch backend: lazily; numpy backend: at once).  The numpy backend takes and returns numpy
+        arrays; the torch backend returns device tensors and does not synchronise the host."""
+        import torch
+
+        sigma = float(sigma)
+        if not 0.0 < sigma < float("inf"):
+            raise ValueError(f"sigma must be positive and finite, got {sigma}")
+        bits, p, map_ids, ids = self._pose_query(particles, env_ids)
+        lidar, err = self._t["lidar"], self._t["err"]
+        observed = (lidar if ids is None else lidar[ids.clamp(0, self.num_envs - 1)]).contiguous()
+        scores = lidar_pose_scores(bits, self.dataset.map_width, p, observed, map_ids, beams=self.lidar_beam_count,
+                                   lidar_range=self.lidar_range, err=err, beam_dirs=self._t["beam_dirs"])
+
+        def dev_f32(x):
+            return None if x is None else torch.as_tensor(x, dtype=torch.float32, device=self._dev).contiguous()
+
+        res = lidar_pf_resample(p, dev_f32(logw), scores, score_scale=np.float32(1.0 / (2.0 * sigma * sigma)),
+                                u=dev_f32(u), ess_frac=ess_frac, err=err)
+        out = PfUpdateResult(*res, scores)
+        if self.array_backend != "numpy":
+            return out
+        out = PfUpdateResult(*(v.cpu().numpy() for v in out))
+        self.check_errors(block=True)
+        return out
+
     def _launch_step(self, a_t, p_t):
         if self.use_torch_op:
             self._step_op(self._h, a_t, p_t)
@@ -769,10 +804,11 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             raise N.ApgError("an autoreset found no prefetched map (prefetch protocol violated)")
         if bits & N.APG_ERR_INDEX:
             raise IndexError("unpack_maps() / scan_poses() / pose_scores(): an env id outside [0, num_envs)"
-                             " (lookahead() too)")
+                             " (lookahead() and pf_update() too)")
         if bits & N.APG_ERR_BAD_POSE:
             raise ValueError("scan_poses() / pose_scores(): a pose with a non-finite coordinate"
-                             " (lookahead(): a non-finite action)")
+                             " (lookahead(): a non-finite action; pf_update(): a particle with a non-finite"
+                             " coordinate or a NaN or +inf log-weight)")
 
     def check_errors(self, block: bool = True):
         """Raise the reference's exception for any error flagged by the kernels so far."""

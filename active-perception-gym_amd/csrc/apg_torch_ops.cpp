@@ -17,6 +17,9 @@
 //   torch.ops.apgym.lidar_move_poses(Tensor bits, int width, Tensor poses, Tensor actions, Tensor? map_ids,
 //                                    Tensor? max_steps, Tensor? origin, Tensor? origin_alias, Tensor pos, Tensor steps,
 //                                    Tensor terminated, Tensor? base_reward, Tensor? odometry, Tensor? err) -> ()
+//   torch.ops.apgym.lidar_pf_resample(Tensor poses, Tensor? logw, Tensor? score, Tensor? u, float score_scale,
+//                                     float ess_frac, Tensor? weight, Tensor? estimate, Tensor? ess, Tensor? index,
+//                                     Tensor? poses_out, Tensor? logw_out, Tensor? resampled, Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -369,6 +372,60 @@ void lidar_move_poses(const at::Tensor &bits, int64_t width, const at::Tensor &p
   check(apg_lidar_move_poses(&a, stream_of(dev)), "apg_lidar_move_poses");
 }
 
+// Particle weights, estimate, ESS and systematic resampling (apg_lidar_pf_resample).  poses: float32 [M, K, 2]; logw,
+// score: float32 [M, K] or None; u: float32 [M] or None (ess_frac <= 0); weight, logw_out: float32 [M, K]; estimate:
+// float32 [M, 2]; ess: float32 [M]; index: int32 [M, K]; poses_out: float32 [M, K, 2]; resampled: uint8 [M]; err:
+// int32 [1]; every output or None.  logw_out may be logw itself.
+void lidar_pf_resample(const at::Tensor &poses, const c10::optional<at::Tensor> &logw,
+                       const c10::optional<at::Tensor> &score, const c10::optional<at::Tensor> &u, double score_scale,
+                       double ess_frac, const c10::optional<at::Tensor> &weight,
+                       const c10::optional<at::Tensor> &estimate, const c10::optional<at::Tensor> &ess,
+                       const c10::optional<at::Tensor> &index, const c10::optional<at::Tensor> &poses_out,
+                       const c10::optional<at::Tensor> &logw_out, const c10::optional<at::Tensor> &resampled,
+                       const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(poses.is_cuda(), "poses must be on a GPU device, got ", poses.device());
+  const at::Device dev = poses.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(poses.dim() == 3 && poses.size(2) == 2, "poses must be [M, K, 2]");
+  const int64_t m = poses.size(0), k = poses.size(1);
+  TORCH_CHECK(k >= 1 && k <= 4096, "poses: K must be in 1..4096, got ", k);
+  check_io(poses, dev, 2 * m * k, "poses");
+  apg_pf_resample_args a{};
+  a.poses = reinterpret_cast<const float *>(ptr(poses));
+  auto f32 = [&](const c10::optional<at::Tensor> &x, int64_t numel, const char *name) -> float * {
+    if (!x.has_value() || !x->defined()) return nullptr;
+    check_io(*x, dev, numel, name);
+    return reinterpret_cast<float *>(ptr(*x));
+  };
+  auto typed = [&](const c10::optional<at::Tensor> &x, at::ScalarType st, int64_t numel, const char *name) -> void * {
+    if (!x.has_value() || !x->defined()) return nullptr;
+    TORCH_CHECK(x->device() == dev && x->scalar_type() == st && x->is_contiguous() && x->numel() == numel, name,
+                " must be a contiguous ", st, " tensor of ", numel, " elements on ", dev);
+    return ptr(*x);
+  };
+  a.logw = f32(logw, m * k, "logw");
+  a.score = f32(score, m * k, "score");
+  a.u = f32(u, m, "u");
+  a.weight = f32(weight, m * k, "weight");
+  a.estimate = f32(estimate, 2 * m, "estimate");
+  a.ess = f32(ess, m, "ess");
+  a.index = reinterpret_cast<int32_t *>(typed(index, at::kInt, m * k, "index"));
+  a.poses_out = f32(poses_out, 2 * m * k, "poses_out");
+  a.logw_out = f32(logw_out, m * k, "logw_out");
+  a.resampled = reinterpret_cast<uint8_t *>(typed(resampled, at::kByte, m, "resampled"));
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    a.err = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  a.m = m;
+  a.k = (int32_t)k;
+  a.score_scale = (float)score_scale;
+  a.ess_frac = (float)ess_frac;
+  if (m == 0) return;
+  check(apg_lidar_pf_resample(&a, stream_of(dev)), "apg_lidar_pf_resample");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -392,4 +449,8 @@ TORCH_LIBRARY(apgym, m) {
         "Tensor? origin, Tensor? origin_alias, Tensor(a!) pos, Tensor(b!) steps, Tensor(c!) terminated, "
         "Tensor(d!)? base_reward, Tensor(e!)? odometry, Tensor(f!)? err) -> ()",
         lidar_move_poses);
+  m.def("lidar_pf_resample(Tensor poses, Tensor? logw, Tensor? score, Tensor? u, float score_scale, "
+        "float ess_frac, Tensor(a!)? weight, Tensor(b!)? estimate, Tensor(c!)? ess, Tensor(d!)? index, "
+        "Tensor(e!)? poses_out, Tensor(f!)? logw_out, Tensor(g!)? resampled, Tensor(h!)? err) -> ()",
+        lidar_pf_resample);
 }

@@ -25,6 +25,8 @@
  *   apg_lidar_move_poses
  *       the movement of LIDARLocalization2DEnv._step  ap_gym/envs/lidar_localization2d.py:330-375 and TimeLimit's
  *       termination, for candidate actions from poses the caller chooses (no env state is advanced)
+ *   apg_lidar_pf_resample
+ *       nothing of the reference: the weight / estimate / resampling stage of a particle filter over the two above
  *   apg_lidar_render_track
  *       the render-only state of LIDARLocalization2DEnv (observation_map, trajectory, last readings)
  *       ap_gym/envs/lidar_localization2d.py:239-261, 312-313, 326-327, 377-380 used by render() :391-494.
@@ -87,7 +89,8 @@ extern "C" {
 #define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps / apg_lidar_scan_poses / apg_lidar_move_poses: a map id
                                      outside [0, n_src) (raised as IndexError) */
 #define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses / apg_lidar_move_poses: a pose (or a candidate action) with a
-                                     non-finite coordinate (raised as ValueError) */
+                                     non-finite coordinate; apg_lidar_pf_resample: a particle with such a pose or with a
+                                     NaN or +inf log-weight (raised as ValueError) */
 
 #define APG_MAP_ROOMS 0
 #define APG_MAP_MAZE 1
@@ -364,6 +367,58 @@ typedef struct apg_move_poses_args {
   int32_t height, width, k, t;
 } apg_move_poses_args;
 int apg_lidar_move_poses(const apg_move_poses_args *args, apg_stream_t stream);
+
+/* Particle weights, the weighted-mean pose, the effective sample size and exact systematic resampling: the third
+ * stage of a particle filter over apg_lidar_scan_poses' scores and apg_lidar_move_poses (an addition to ABI 0.4; no
+ * changes to existing structs).  For each set i of m, with k particles in 1..4096; every f32 operation is rounded on
+ * its own:
+ *   1 log-weight    l_j = logw[i][j] - score_scale * score[i][j]: one f32 multiply, then one f32 subtract.  logw NULL:
+ *                   all 0; score NULL: l_j = logw[i][j].
+ *   2 bad           a particle is bad when l_j is NaN or +inf or its pose has a non-finite coordinate: weight 0,
+ *                   logw_out -inf, never selected, APG_ERR_BAD_POSE OR-ed into *err.  -inf is legal: a dead particle,
+ *                   weight 0, no flag.
+ *   3 weight        l_max = the maximum of l_j over the particles that are not bad; d_j = l_j - l_max in f32;
+ *                   weight[i][j] = expf(d_j), so the maximum has weight exactly 1.  l_max not finite (no particle
+ *                   alive): every particle that is not bad has d_j = 0 and weight 1, a uniform restart.
+ *   4 integers      q_j = (uint32) rintf(weight[i][j] * 16777216.0f), round half to even, in 0..2^24; Q = sum q_j and
+ *                   S2 = sum q_j^2 in uint64 (Q <= 2^36, S2 <= 2^60: exact, independent of order).
+ *   5 estimate      estimate[i] = (float)(sum_j (double)q_j * (double)pose_j / (double)Q) per coordinate, over the
+ *                   particles with q_j > 0 (the order of the f64 sum is the implementation's, fixed from run to run);
+ *                   NaN when Q == 0 (every particle bad).
+ *   6 ESS           ess64 = (double)Q * (double)Q / (double)S2; ess[i] = (float)ess64, 0 when Q == 0.
+ *   7 decision      the set is resampled iff Q > 0 and ess64 < (double)ess_frac * (double)k.  ess_frac <= 0 or NaN:
+ *                   never.  Uniform weights give ess64 == k exactly: ess_frac = 1 resamples every set but the
+ *                   uniform ones, a value above 1 every set.
+ *   8 resampling    systematic, in integers: U = floor(u[i] * 2^24) clamped to 0..2^24 - 1 (0 for a NaN);
+ *                   T_j = floor(j Q / k) + floor(U Q / (k 2^24)) in uint64 (< Q; nothing exceeds 2^60);
+ *                   C_a = q_0 + ... + q_a; index[i][j] = the smallest a with C_a > T_j: nondecreasing in j, never a
+ *                   particle with q_a == 0, particle a copied floor(k q_a / Q) or ceil(k q_a / Q) times.
+ *   9 outputs                       resampled set              other set
+ *       index[i][j] (int32)         the ancestor               j
+ *       poses_out[i][j]             poses[i][index[i][j]]      poses[i][j]
+ *       logw_out[i][j]              0.0                        d_j, -inf for a bad particle
+ *     resampled[i] (uint8) holds the decision.  Every output pointer may be NULL.
+ * Aliasing: poses_out must not overlap poses; logw_out may be exactly logw (in place), a partial overlap is invalid.
+ * u may be NULL only when ess_frac <= 0 (or NaN).  k outside 1..4096, poses NULL, m < 0 and the cases above are
+ * APG_E_INVALID without a GPU call; m == 0 launches nothing.  Every index is in [0, k) whatever the inputs hold. */
+typedef struct apg_pf_resample_args {
+  const float *logw;    /* [m][k] or NULL */
+  const float *score;   /* [m][k] or NULL */
+  const float *poses;   /* [m][k][2] (x, y) */
+  const float *u;       /* [m] in [0, 1), or NULL when ess_frac <= 0 */
+  float *weight;        /* [m][k] or NULL */
+  float *estimate;      /* [m][2] or NULL */
+  float *ess;           /* [m] or NULL */
+  int32_t *index;       /* [m][k] or NULL */
+  float *poses_out;     /* [m][k][2] or NULL */
+  float *logw_out;      /* [m][k] or NULL; may be logw */
+  uint8_t *resampled;   /* [m] or NULL */
+  uint32_t *err;        /* or NULL */
+  int64_t m;
+  int32_t k;
+  float score_scale, ess_frac;
+} apg_pf_resample_args;
+int apg_lidar_pf_resample(const apg_pf_resample_args *args, apg_stream_t stream);
 
 /* ---------------------------------------------------------------- LIDAR render path (not the hot path)
  * Render-only state of the tracked sub-envs: what LIDARLocalization2DEnv keeps for render()
