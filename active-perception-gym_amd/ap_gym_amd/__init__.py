@@ -41,6 +41,7 @@ from .move_poses import MovePosesResult, lidar_move_poses  # noqa: F401
 from .particle_filter import LidarParticleFilter  # noqa: F401
 from .pf_resample import PfResampleResult, lidar_pf_resample  # noqa: F401
 from .scan_poses import lidar_pose_scores, lidar_scan_poses  # noqa: F401
+from .scan_spread import ScanSpreadResult, lidar_scan_spread  # noqa: F401
 from .registration import make_vec, register, registry  # noqa: F401
 from .spaces import ActivePerceptionActionSpace, ImageSpace, LogitSpace  # noqa: F401
 

@@ -33,6 +33,7 @@ APG_ERR_NO_FREE_CELL = 64
 APG_ERR_INDEX = 128  # unpack_maps / scan_poses / move_poses: a map id outside [0, n_src) (raised as IndexError)
 APG_ERR_BAD_POSE = 256  # scan_poses / move_poses: a pose or candidate action with a non-finite coordinate (ValueError)
 #                         pf_resample: a particle with such a pose, or with a NaN or +inf log-weight
+#                         scan_spread: a hypothesis with such a pose, or with a weight that is NaN or outside [0, 1]
 # k_scan_poses' work split (csrc/apg_scan_poses.hip SP_TILE, SP_MAX_MPW, SP_MAX_GRID): rays per workgroup pass, pose
 # sets a workgroup takes at once when a set is small, workgroups per launch
 SCAN_POSES_TILE = 256
@@ -54,6 +55,13 @@ PF_RESAMPLE_TILE = 256
 PF_RESAMPLE_SETS_PER_WG = PF_RESAMPLE_TILE // 64
 PF_RESAMPLE_MAX_K = 4096
 PF_RESAMPLE_MAX_GRID = 65536
+# k_scan_spread's work split (csrc/apg_scan_spread.hip SS_TILE, SS_MAX_K, SS_MAX_BEAMS, SS_MAX_GRID): rays per
+# workgroup pass (a set is walked in tiles of max(1, tile // beams) poses), hypotheses per set, beams, workgroups per
+# launch (each takes a contiguous run of ceil(M * A / grid) (set, candidate) items)
+SCAN_SPREAD_TILE = 256
+SCAN_SPREAD_MAX_K = 4096
+SCAN_SPREAD_MAX_BEAMS = 1024
+SCAN_SPREAD_MAX_GRID = 8192
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -135,6 +143,13 @@ class PfResampleArgs(ctypes.Structure):
     _fields_ = [(n, _vp) for n in ("logw", "score", "poses", "u", "weight", "estimate", "ess", "index", "poses_out",
                                    "logw_out", "resampled", "err")] + [
         ("m", ctypes.c_int64), ("k", ctypes.c_int32), ("score_scale", ctypes.c_float), ("ess_frac", ctypes.c_float)]
+
+
+class ScanSpreadArgs(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("occ", "map_ids", "poses", "beam_dirs", "weight", "spread", "mean", "err")] + [
+        ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ("height", "width", "a", "k", "beams")] + [
+        ("lidar_range", ctypes.c_float)]
 
 
 class LidarSizes(ctypes.Structure):
@@ -222,6 +237,7 @@ SYMBOLS = [
     ("apg_lidar_scan_poses", ctypes.c_int, [ctypes.POINTER(ScanPosesArgs), _vp]),
     ("apg_lidar_move_poses", ctypes.c_int, [ctypes.POINTER(MovePosesArgs), _vp]),
     ("apg_lidar_pf_resample", ctypes.c_int, [ctypes.POINTER(PfResampleArgs), _vp]),
+    ("apg_lidar_scan_spread", ctypes.c_int, [ctypes.POINTER(ScanSpreadArgs), _vp]),
     ("apg_lidar_render_track", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp,
                                               ctypes.POINTER(LidarOutputs), ctypes.POINTER(LidarRenderState), _vp]),
     ("apg_rng_draws", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

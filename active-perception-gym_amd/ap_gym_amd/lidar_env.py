@@ -67,6 +67,7 @@ from .map_bits import host_words_np, unpack_map_bits, words_per_row
 from .move_poses import lidar_move_poses
 from .pf_resample import PfUpdateResult, lidar_pf_resample
 from .scan_poses import lidar_pose_scores, lidar_scan_poses
+from .scan_spread import lidar_scan_spread
 from .spaces import ActivePerceptionActionSpace, Box, Dict, ImageSpace, batch_space
 from .vector_env import VectorEnv
 
@@ -769,6 +770,54 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         self.check_errors(block=True)
         return out
 
+    def action_spread(self, particles, actions, weight=None, env_ids=None, *, mean: bool = False):
+        """How much would a belief's hypotheses disagree about what they see after each candidate action?
+        `particles` [M, K, 2] ((x, y) in cells, K hypotheses for each of the sub-envs `env_ids`; None: every sub-env),
+        `actions` [M, A, 2] or [M, A, T, 2] (A candidates of T actions each), `weight` [M, K] in [0, 1] (None: all 1).
+        Every particle makes the env's own move under every candidate (move_poses.lidar_move_poses on the [M, A * K]
+        expansion, without a step limit, as LidarParticleFilter.predict moves them), and the final poses go to
+        scan_spread.lidar_scan_spread: two launches, no scan written to memory.  Returns a dict:
+
+          spread      [M, A] the weighted variance of the hypotheses' normalised scans, summed over the beams: half the
+                      expected pose_scores() value between two hypotheses drawn from the belief; exactly 0 where they
+                      all read the same scan, NaN where no hypothesis has positive weight
+          mean        [M, A, beams] the belief's expected scan (mean=True only)
+          pos         [M, A, K, 2] the final pose of each particle under each candidate
+          terminated  bool [M, A, K]: the particle left the map under the candidate
+
+        Works in both map_obs modes and for every map source, and changes no env state.  A particle or action with a
+        non-finite coordinate drops out of its own (m, a) only, a weight that is NaN or outside [0, 1] counts as 0,
+        and both raise ValueError, an env id outside [0, num_envs) IndexError, through check_errors() (torch backend:
+        lazily; numpy backend: at once).  The numpy backend takes and returns numpy arrays; the torch backend returns
+        device tensors and does not synchronise the host."""
+        import torch
+
+        bits, p, map_ids, _ = self._pose_query(particles, env_ids)
+        m, k = p.shape[0], p.shape[1]
+        a = torch.as_tensor(actions, dtype=torch.float32, device=self._dev)
+        if a.dim() == 3:
+            a = a.unsqueeze(2)
+        if a.dim() != 4 or a.shape[3] != 2 or a.shape[0] != m:
+            raise ValueError(f"actions must have shape [{m}, A, T, 2] or [{m}, A, 2], got {tuple(a.shape)}")
+        na, t = a.shape[1], a.shape[2]
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self._dev).contiguous()
+        w, err = self.dataset.map_width, self._t["err"]
+        start = p[:, None, :, :].expand(m, na, k, 2).reshape(m, na * k, 2)
+        acts = a[:, :, None, :, :].expand(m, na, k, t, 2).reshape(m, na * k, t, 2)
+        moved = lidar_move_poses(bits, w, start, acts, map_ids, base_reward=False, err=err)
+        pos = moved.pos[:, :, -1, :].reshape(m, na, k, 2).contiguous()
+        res = lidar_scan_spread(bits, w, pos, weight, map_ids, beams=self.lidar_beam_count,
+                                lidar_range=self.lidar_range, mean=mean, err=err, beam_dirs=self._t["beam_dirs"])
+        out = dict(spread=res.spread, pos=pos, terminated=moved.terminated.view(m, na, k).bool())
+        if mean:
+            out["mean"] = res.mean
+        if self.array_backend != "numpy":
+            return out
+        out = {name: v.cpu().numpy() for name, v in out.items()}
+        self.check_errors(block=True)
+        return out
+
     def _launch_step(self, a_t, p_t):
         if self.use_torch_op:
             self._step_op(self._h, a_t, p_t)
@@ -804,11 +853,12 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             raise N.ApgError("an autoreset found no prefetched map (prefetch protocol violated)")
         if bits & N.APG_ERR_INDEX:
             raise IndexError("unpack_maps() / scan_poses() / pose_scores(): an env id outside [0, num_envs)"
-                             " (lookahead() and pf_update() too)")
+                             " (lookahead(), pf_update() and action_spread() too)")
         if bits & N.APG_ERR_BAD_POSE:
             raise ValueError("scan_poses() / pose_scores(): a pose with a non-finite coordinate"
                              " (lookahead(): a non-finite action; pf_update(): a particle with a non-finite"
-                             " coordinate or a NaN or +inf log-weight)")
+                             " coordinate or a NaN or +inf log-weight; action_spread(): a particle or action with a"
+                             " non-finite coordinate, or a weight that is NaN or outside [0, 1])")
 
     def check_errors(self, block: bool = True):
         """Raise the reference's exception for any error flagged by the kernels so far."""

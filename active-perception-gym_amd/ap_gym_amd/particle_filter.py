@@ -14,6 +14,9 @@
         pf.predict(action)
         pf.update()
 
+`pf.choose_action(candidates)` closes the loop from the belief to the next action: the candidate after which the
+particles would disagree most about what they see (lidar_scan_spread, two more launches).
+
 The filter reads the env's device buffers (occupancy rows, obs["lidar"], reset_mask): it works on a torch-backend
 LIDARLocalization2DVectorEnv, in both map_obs modes and for every map source.  ShardedVectorEnv does not forward it
 (build one filter per shard's env).
@@ -125,6 +128,29 @@ class LidarParticleFilter:
         res = self.env.pf_update(self.particles, self.logw, sigma=self.sigma, ess_frac=self.ess_frac, u=u)
         self.particles, self.logw, self.last = res.poses, res.logw, res
         return res
+
+    def action_spread(self, candidates, *, mean: bool = False):
+        """env.action_spread of the filter's particles with the weights exp(logw), for the candidate actions
+        `candidates` float32 [num_envs, A, 2] or [num_envs, A, T, 2]: how much the belief's hypotheses would disagree
+        about what they see after each candidate.  Changes neither the filter nor the env."""
+        import torch
+
+        if self.particles is None:
+            raise RuntimeError("call reset() first")
+        return self.env.action_spread(self.particles, candidates, torch.exp(self.logw), mean=mean)
+
+    def choose_action(self, candidates):
+        """The candidate that tells the belief's hypotheses apart best: (action [num_envs, 2], spread [num_envs, A]),
+        where `action` is the first action of the candidate with the largest spread (the lowest index among equals).
+        A NaN spread (no particle of positive weight under that candidate) never wins; where every spread is NaN the
+        first candidate is returned."""
+        import torch
+
+        c = torch.as_tensor(candidates, dtype=torch.float32, device=self._dev)
+        spread = self.action_spread(c)["spread"]
+        best = torch.where(torch.isnan(spread), torch.full_like(spread, -1.0), spread).argmax(dim=1)  # (spread >= 0)
+        first = c if c.dim() == 3 else c[:, :, 0, :]
+        return first[torch.arange(first.shape[0], device=self._dev), best], spread
 
     @property
     def estimate(self):

@@ -426,6 +426,69 @@ void lidar_pf_resample(const at::Tensor &poses, const c10::optional<at::Tensor> 
   check(apg_lidar_pf_resample(&a, stream_of(dev)), "apg_lidar_pf_resample");
 }
 
+// The scan spread of a particle belief per candidate action (apg_lidar_scan_spread).  bits: int64
+// [n_src, H, ceil(width / 64)]; poses: float32 [M, A, K, 2]; weight: float32 [M, K] or None; map_ids: int64 [M] or
+// None; beam_dirs: float32 [B, 2]; spread: float32 [M, A] or None; mean: float32 [M, A, B] or None; err: int32 [1] or
+// None.
+void lidar_scan_spread(const at::Tensor &bits, int64_t width, const at::Tensor &poses,
+                       const c10::optional<at::Tensor> &weight, const c10::optional<at::Tensor> &map_ids,
+                       const at::Tensor &beam_dirs, double lidar_range, const c10::optional<at::Tensor> &spread,
+                       const c10::optional<at::Tensor> &mean, const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(bits.is_cuda(), "bits must be on a GPU device, got ", bits.device());
+  const at::Device dev = bits.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(bits.scalar_type() == at::kLong && bits.dim() == 3 && bits.is_contiguous(),
+              "bits must be a contiguous int64 [n_src, H, ceil(width / 64)] tensor");
+  TORCH_CHECK(width >= 1 && width <= 511 && bits.size(2) == (width + 63) / 64, "bits has ", bits.size(2),
+              " words per row, width ", width, " needs ", (width + 63) / 64, " (width 1..511)");
+  TORCH_CHECK(poses.dim() == 4 && poses.size(3) == 2, "poses must be [M, A, K, 2]");
+  const int64_t m = poses.size(0), na = poses.size(1), k = poses.size(2);
+  TORCH_CHECK(na >= 1 && na <= INT32_MAX, "poses: A must be >= 1, got ", na);
+  TORCH_CHECK(k >= 1 && k <= 4096, "poses: K must be in 1..4096, got ", k);
+  check_io(poses, dev, 2 * m * na * k, "poses");
+  TORCH_CHECK(beam_dirs.dim() == 2 && beam_dirs.size(1) == 2, "beam_dirs must be [B, 2]");
+  const int64_t b = beam_dirs.size(0);
+  TORCH_CHECK(b >= 1 && b <= 1024, "beam_dirs: B must be in 1..1024, got ", b);
+  check_io(beam_dirs, dev, 2 * b, "beam_dirs");
+  apg_scan_spread_args a{};
+  a.occ = reinterpret_cast<const uint64_t *>(ptr(bits));
+  a.poses = reinterpret_cast<const float *>(ptr(poses));
+  a.beam_dirs = reinterpret_cast<const float *>(ptr(beam_dirs));
+  if (weight.has_value() && weight->defined()) {
+    check_io(*weight, dev, m * k, "weight");
+    a.weight = reinterpret_cast<const float *>(ptr(*weight));
+  }
+  if (map_ids.has_value() && map_ids->defined()) {
+    TORCH_CHECK(map_ids->device() == dev && map_ids->scalar_type() == at::kLong && map_ids->dim() == 1 &&
+                    map_ids->is_contiguous() && map_ids->numel() == m,
+                "map_ids must be a contiguous int64 [M] tensor on ", dev);
+    a.map_ids = reinterpret_cast<const int64_t *>(ptr(*map_ids));
+  }
+  if (spread.has_value() && spread->defined()) {
+    check_io(*spread, dev, m * na, "spread");
+    a.spread = reinterpret_cast<float *>(ptr(*spread));
+  }
+  if (mean.has_value() && mean->defined()) {
+    check_io(*mean, dev, m * na * b, "mean");
+    a.mean = reinterpret_cast<float *>(ptr(*mean));
+  }
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    a.err = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  a.n_src = bits.size(0);
+  a.m = m;
+  a.height = (int32_t)bits.size(1);
+  a.width = (int32_t)width;
+  a.a = (int32_t)na;
+  a.k = (int32_t)k;
+  a.beams = (int32_t)b;
+  a.lidar_range = (float)lidar_range;
+  if (m == 0) return;
+  check(apg_lidar_scan_spread(&a, stream_of(dev)), "apg_lidar_scan_spread");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -453,4 +516,7 @@ TORCH_LIBRARY(apgym, m) {
         "float ess_frac, Tensor(a!)? weight, Tensor(b!)? estimate, Tensor(c!)? ess, Tensor(d!)? index, "
         "Tensor(e!)? poses_out, Tensor(f!)? logw_out, Tensor(g!)? resampled, Tensor(h!)? err) -> ()",
         lidar_pf_resample);
+  m.def("lidar_scan_spread(Tensor bits, int width, Tensor poses, Tensor? weight, Tensor? map_ids, Tensor beam_dirs, "
+        "float lidar_range, Tensor(a!)? spread, Tensor(b!)? mean, Tensor(c!)? err) -> ()",
+        lidar_scan_spread);
 }

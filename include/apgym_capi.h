@@ -420,6 +420,52 @@ typedef struct apg_pf_resample_args {
 } apg_pf_resample_args;
 int apg_lidar_pf_resample(const apg_pf_resample_args *args, apg_stream_t stream);
 
+/* The scan spread of a particle belief per candidate action: how much the hypotheses of a belief would disagree about
+ * what they see, the quantity an active localiser maximises over its candidates (an addition to ABI 0.4; no changes
+ * to existing structs).  For each set i of m and each candidate c of a: k hypotheses with the poses poses[i][c][*]
+ * (hypothesis j after candidate c) and the weights weight[i][*], on map map_ids[i] of occ (the packed layout above; the
+ * padding bits at x >= width are ignored), along the `beams` directions of beam_dirs.  The result is the weighted
+ * variance of the hypotheses' normalised scans, summed over the beams; with normalised weights w,
+ * sum_jk w_j w_k |z_j - z_k|^2 = 2 sum_b Var_w(z_b), so it is half the expected apg_lidar_scan_poses score between two
+ * hypotheses drawn from the belief.  No scan is written to memory, and every sum is an exact integer: the result does
+ * not depend on the order of any reduction.  Every f32 and f64 operation is rounded on its own:
+ *   1 weight     q_j = (uint32) rintf(weight[i][j] * 16777216.0f), round half to even, in 0..2^24: the integer weight
+ *                of apg_lidar_pf_resample.  weight NULL: every q_j = 2^24.  A weight that is NaN, below 0 or above 1:
+ *                q_j = 0 and APG_ERR_BAD_POSE is OR-ed into *err.
+ *   2 scan       s_jb = the normalised scan of pose (i, c, j) along beam b: exactly apg_lidar_scan_poses with
+ *                normalize != 0 (the same scan, the same rule for poses further than 64 cells outside the map, the same
+ *                all-zero map and APG_ERR_INDEX for a map id outside [0, n_src)).  A pose with a non-finite coordinate
+ *                is not scanned: it counts with q_j = 0 for this (i, c) only, and APG_ERR_BAD_POSE is set.  A beam
+ *                direction with a non-finite component or one beyond 60 cells is not scanned either: its v_jb is 0 for
+ *                every pose, and APG_ERR_BAD_POSE is set.
+ *   3 quantise   v_jb = (int32) rintf(s_jb * 4096.0f): the product is exact, the rounding half to even, |v_jb| <= 4096.
+ *   4 sums       S0 = sum_j q_j (<= 2^36); S1_b = sum_j q_j v_jb (|S1_b| <= 2^48, int64); S2_b = sum_j q_j v_jb^2
+ *                (<= 2^60, uint64): exact integers, independent of order.
+ *   5 per beam   N_b = S0 S2_b - S1_b^2 in unsigned __int128 (>= 0 by Cauchy-Schwarz; both products <= 2^96);
+ *                N = sum_b N_b (<= 2^106).
+ *   6 spread     spread[i][c] = (float)(((double)N / ((double)S0 * (double)S0)) * 0x1p-24): the conversion of N rounds
+ *                to nearest even, then one f64 multiply, one f64 divide and the exact scale.  NaN when S0 == 0.  The
+ *                result is exactly 0 iff every hypothesis with q_j > 0 reads the same quantised scan.
+ *   7 mean       mean[i][c][b] = (float)(((double)S1_b / (double)S0) * 0x1p-12), the belief's expected scan.  NaN when
+ *                S0 == 0.
+ * Either output may be NULL (not both).  Limits: k 1..4096, a >= 1, beams 1..1024 (the per-beam sums live in LDS),
+ * height and width 1..511, 0 < lidar_range <= 60; map_ids NULL needs n_src == 1 or m <= n_src.  A violation is
+ * APG_E_INVALID without a GPU call; m == 0 launches nothing. */
+typedef struct apg_scan_spread_args {
+  const uint64_t *occ;      /* [n_src][height][ceil(width/64)], layout of apg_lidar_state.occ */
+  const int64_t *map_ids;   /* [m] or NULL: map i, or map 0 for every set when n_src == 1 */
+  const float *poses;       /* [m][a][k][2] (x, y) in cells */
+  const float *beam_dirs;   /* [beams][2], each no longer than lidar_range */
+  const float *weight;      /* [m][k] in [0, 1], or NULL (all 1) */
+  float *spread;            /* [m][a] or NULL */
+  float *mean;              /* [m][a][beams] or NULL */
+  uint32_t *err;            /* or NULL */
+  int64_t n_src, m;
+  int32_t height, width, a, k, beams;
+  float lidar_range;
+} apg_scan_spread_args;
+int apg_lidar_scan_spread(const apg_scan_spread_args *args, apg_stream_t stream);
+
 /* ---------------------------------------------------------------- LIDAR render path (not the hot path)
  * Render-only state of the tracked sub-envs: what LIDARLocalization2DEnv keeps for render()
  * (ap_gym/envs/lidar_localization2d.py:391-494) — observation_map (:239-261, :301), the trajectory deque
