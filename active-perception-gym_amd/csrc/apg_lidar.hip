@@ -2669,8 +2669,8 @@ int apg_map_generate(int map_kind, const uint64_t *idx, int n, int h, int w, int
 
 int apg_lidar_scan_batch(const uint64_t *occ, const int32_t *map_index, int h, int w, const float *seg, int n,
                          float *dist, int32_t *kind, apg_stream_t stream) {
-  if (n <= 0 || h <= 0 || w <= 0 || w > 255) return fail(APG_E_INVALID, "bad scan batch arguments");
-  // segments must span <= 28 columns (32-column row window); callers check this on the host
+  if (n <= 0 || h <= 0 || w <= 0 || h > 511 || w > 511) return fail(APG_E_INVALID, "bad scan batch arguments");
+  // segments must span <= 61 columns (RowsGlobal's 64-column row window); callers check this on the host
   hipLaunchKernelGGL(k_scan_batch, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, occ, map_index, h,
                      w, (w + 63) / 64, seg, n, dist, kind);
   return check_launch("k_scan_batch");

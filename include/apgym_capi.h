@@ -275,7 +275,8 @@ int apg_map_generate(int map_kind, const uint64_t *idx, int n, int h, int w, int
                      int door_width, double branching_prob, uint64_t *occ, uint64_t *scratch,
                      uint16_t *stack, uint32_t *err, apg_stream_t stream);
 
-/* n segments seg[n][4] = (px, py, qx, qy) against map map_index[n] of occ[*][h][wpr]. */
+/* n segments seg[n][4] = (px, py, qx, qy) against map map_index[n] of occ[*][h][wpr]; h and w in 1..511, every
+ * segment at most 61 columns wide (one 64-column row window). */
 int apg_lidar_scan_batch(const uint64_t *occ, const int32_t *map_index, int h, int w,
                          const float *seg, int n, float *dist, int32_t *kind, apg_stream_t stream);
 

@@ -9,9 +9,11 @@ Sources of truth, per fixture:
   loss.npz         the reference's MSELossFn / CrossEntropyLossFn (normalized as the envs build them).
   lidar_scan.npz   the reference's LIDARLocalization2DEnv.__lidar_scan (lidar_localization2d.py:496-536)
                    with tests/golden/_stubs/shapely (exact-rational GEOS model) in place of shapely.
+  lidar_scan_wide.npz  the same scan on maps up to 511 wide or high, for segments up to 60 long.
   lidar_env_*.npz  the reference's LIDARLocalization2DEnv wrapped exactly as registration.py:319-356
                    composes it (TimeLimit(100, issue_termination=True) + ActiveRegressionLogWrapper),
-                   vectorised by the gymnasium SyncVectorEnv restatement in tests/golden/_stubs.
+                   vectorised by the gymnasium SyncVectorEnv restatement in tests/golden/_stubs
+                   (lidar_env_pool72_*: at lidar_range 9.5 .. 60, which the fixture stores).
   image_*.npz      the reference's ImageClassificationVectorEnv / ImageLocalizationVectorEnv
                    (ImagePerceptionModule, scipy RegularGridInterpolator, CE/MSE losses) run as-is on
                    small synthetic uint8 pools (HF datasets are not available offline), seeded through
@@ -184,7 +186,7 @@ def _reset_prediction_info_shim(ap):
 
 
 def run_lidar_env(name, dataset, static, beams, n_envs, steps, seed, action_mode, sparse=False, static_map_index=0,
-                  extra=None):
+                  extra=None, lidar_range=5):
     lmod = _lidar_module()
     gym = sys.modules["gymnasium"]
     ap = sys.modules["ap_gym"]
@@ -192,7 +194,7 @@ def run_lidar_env(name, dataset, static, beams, n_envs, steps, seed, action_mode
 
     def mk():
         env = lmod.LIDARLocalization2DEnv(dataset=dataset, static_map=static, lidar_beam_count=beams,
-                                          prefetch=False, static_map_index=static_map_index)
+                                          prefetch=False, static_map_index=static_map_index, lidar_range=lidar_range)
         env = ap.TimeLimit(env, max_episode_steps=100, issue_termination=True)
         env = ap.ActiveRegressionLogWrapper(env)
         # the "-sparse" ids (registration.py:115-142): SparsifyWrapper over the registered composition
@@ -270,7 +272,8 @@ def run_lidar_env(name, dataset, static, beams, n_envs, steps, seed, action_mode
          reset_lidar=reset_obs["lidar"], reset_odometry=reset_obs["odometry"],
          reset_time_step=reset_obs["time_step"], reset_map_idx=reset_map_idx,
          reset_map=(np.packbits(reset_obs["map"][..., 0] > 0, axis=-1) if "map" in reset_obs
-                    else np.zeros(0, np.uint8)), **arrays, **(extra or {}))
+                    else np.zeros(0, np.uint8)), lidar_range=np.array(lidar_range, np.float64), **arrays,
+         **(extra or {}))
 
 
 def fixed_floor_maps(n=37, h=40, w=48, seed=2024, open_every=0):
@@ -299,11 +302,9 @@ def fixed_floor_maps(n=37, h=40, w=48, seed=2024, open_every=0):
     return maps
 
 
-def make_pool():
-    """LIDAR envs over a user FloorMapDataset subclass (floor_map_dataset.py:10-22): the DatasetIterator draws
-    integers(0, len(dataset)) (dataset_iterator.py:26-32), any H x W."""
+def fixed_floor_maps_dataset():
+    """A user subclass of the reference's FloorMapDataset (floor_map_dataset.py:10-22) over maps bool [n, H, W]."""
     fm = refload.load("envs.floor_map")
-    maps = fixed_floor_maps()
 
     class FixedFloorMaps(fm.FloorMapDataset):
         def __init__(self, m):
@@ -319,8 +320,19 @@ def make_pool():
         def get_data_point_batch(self, idx):
             return self._m[np.asarray(idx)].copy()
 
-    def extra(m):
-        return dict(pool_bits=np.packbits(m, axis=-1), pool_hw=np.array(m.shape[1:]))
+    return FixedFloorMaps
+
+
+def pool_extra(m):
+    return dict(pool_bits=np.packbits(m, axis=-1), pool_hw=np.array(m.shape[1:]))
+
+
+def make_pool():
+    """LIDAR envs over a user FloorMapDataset subclass (floor_map_dataset.py:10-22): the DatasetIterator draws
+    integers(0, len(dataset)) (dataset_iterator.py:26-32), any H x W."""
+    maps = fixed_floor_maps()
+    FixedFloorMaps = fixed_floor_maps_dataset()
+    extra = pool_extra
 
     def first_seed(fn, seeds):
         """fn(seed) for the first seed whose reference run does not raise IndexError: for H != W the reference's
@@ -843,11 +855,200 @@ def make_stream():
     run_lidar_env("stream40_b16", RngFloorMaps(), False, 16, 64, 110, 42, "wide")
 
 
+# --------------------------------------------------------------------------- long-range, wide-map scans
+SCAN_WIDE_MAPS = ((96, 511, 0.02, True), (70, 200, 0.35, True), (511, 67, 0.08, True), (130, 130, 0.004, True),
+                  (64, 129, 0.05, False))  # (H, W, noise, border walls)
+SCAN_WIDE_RANGE = 60.0  # the range the pose group's scans are normalised with (the directions are 1..60 long)
+SCAN_WIDE_POSES, SCAN_WIDE_FREE = 48, 1300  # poses per map (x 40 directions), free segments per map
+
+
+def _ulps(x, k):
+    """float32 x moved by k units in the last place."""
+    x = np.float32(x)
+    for _ in range(abs(int(k))):
+        x = np.nextafter(x, np.float32(np.inf if k > 0 else -np.inf))
+    return x
+
+
+def _scan_wide_dirs(rng):
+    """float32 [40, 2]: arbitrary angles at lengths 1..60, exact axis and diagonal directions, directions a few 1e-7
+    rad off an axis or a diagonal, integer vectors; every component at most 60."""
+    d = []
+    lengths = np.concatenate([[1.0, 2.5, 59.5], rng.uniform(1, 60, 11)])
+    for ln, a in zip(lengths, rng.uniform(-np.pi, np.pi, 14)):
+        d.append((ln * np.cos(a), ln * np.sin(a)))
+    d += [(60, 0), (0, -60), (-float(rng.integers(1, 60)), 0), (0, rng.uniform(1, 60))]
+    ln = rng.uniform(1, 42, 2)
+    d += [(42, 42), (-ln[0], ln[0]), (ln[1], -ln[1]), (-3, -3)]
+    for base, ln in ((0, 57), (np.pi / 2, 31), (np.pi, 44), (np.pi / 4, 59), (-3 * np.pi / 4, 23), (3 * np.pi / 4, 50)):
+        e = rng.choice([-1, 1]) * rng.uniform(1e-7, 5e-7)
+        d.append((ln * np.cos(base + e), ln * np.sin(base + e)))
+    for v, n in (((2, 1), 26), ((2, 1), 3), ((-2, -1), 11), ((3, -2), 16), ((-3, 2), 5), ((3, -2), 1), ((5, 1), 11),
+                 ((-5, -1), 4), ((1, 5), 9), ((1, 2), 20), ((-1, 3), 15), ((2, -3), 7)):
+        d.append((v[0] * n, v[1] * n))
+    d = np.array(d, np.float64)[rng.permutation(len(d))].astype(np.float32)
+    assert d.shape == (40, 2) and np.abs(d).max() <= 60 and np.hypot(d[:, 0], d[:, 1]).max() <= 60
+    return d
+
+
+def _scan_wide_cell(rng, m, free):
+    """(cx, cy) of a free cell (4 in 5) or of any cell."""
+    if rng.random() < 0.8:
+        cy, cx = free[rng.integers(len(free))]
+    else:
+        cy, cx = rng.integers(m.shape[0]), rng.integers(m.shape[1])
+    return np.array([cx, cy], np.float64)
+
+
+def _scan_wide_outside(rng, h, w):
+    """A point up to 3 cells outside the h x w rectangle (every other one on the half-lattice)."""
+    p = np.array([rng.uniform(-3, w + 3), rng.uniform(-3, h + 3)])
+    j = int(rng.integers(2))
+    p[j] = -rng.uniform(0, 3) if rng.random() < 0.5 else (w, h)[j] + rng.uniform(0, 3)
+    return np.round(p * 2) / 2 if rng.random() < 0.5 else p
+
+
+def _scan_wide_poses(rng, m, border, k):
+    """float32 [k, 2], by k % 6: generic points, cell centres, lattice points, half-lattice points, a coordinate one
+    ulp either side of a grid line, and points near a multiple of 64 in x (a borderless map: up to 3 cells outside)."""
+    h, w = m.shape
+    free = np.argwhere(~m)
+    out = np.zeros((k, 2), np.float32)
+    for i in range(k):
+        c = _scan_wide_cell(rng, m, free)
+        mode = i % 6
+        if mode == 0:
+            p = c + rng.uniform(0, 1, 2)
+        elif mode == 1:
+            p = c + 0.5
+        elif mode == 2:
+            p = c + rng.integers(0, 2, 2)
+        elif mode == 3:
+            p = c + np.array([[0, 0.5], [0.5, 0], [1, 0.5], [0.5, 1]])[rng.integers(4)]
+        elif mode == 4:
+            p = (c + rng.uniform(0, 1, 2)).astype(np.float32)
+            for j in ((0,), (1,), (0, 1))[rng.integers(3)]:
+                p[j] = _ulps(c[j] + rng.integers(0, 2), rng.choice([-1, 1]))
+        elif not border:
+            p = _scan_wide_outside(rng, h, w)
+        else:
+            p = np.array([np.clip(64 * rng.integers(1, (w + 63) // 64) + rng.uniform(-2, 2), 1, w - 1),
+                          rng.uniform(1, h - 1)])
+        out[i] = p
+    return out
+
+
+def _scan_wide_free(rng, m, border, n):
+    """float32 [n, 4] segments (px, py, qx, qy), at most 60 long, q within 3 cells of the map rectangle (a draw that
+    is not is made again, so a clipped q does not leave its class).  By i % 10:
+    0-5  near-lattice passes: q beyond a lattice point 1-60 cells from p on the line from p through it (t = 1 or t in
+         (1, 1.3]), then one coordinate of q moved by -2..+2 ulps; every other one of mode 5 starts on the quarter
+         lattice with t in {1.125, 1.25, 1.5}, so that the unmoved q is exact and the line passes through the point
+    6-7  segments ending exactly on lattice points (mode 7: from a lattice point)
+    8-9  short segments (<= 1 cell), at coordinates above 500 where the map has them"""
+    h, w = m.shape
+    free = np.argwhere(~m)
+    out = np.zeros((n, 4), np.float32)
+    i = 0
+    while i < n:
+        mode = i % 10
+        c = _scan_wide_cell(rng, m, free)
+        p = c + rng.uniform(0, 1, 2)
+        if not border and rng.random() < 0.15:
+            p = _scan_wide_outside(rng, h, w)
+        if mode <= 5:
+            exact = mode == 5 and rng.random() < 0.5
+            if exact:
+                p = c + rng.integers(0, 4, 2) * 0.25
+                t = float(rng.choice([1.125, 1.25, 1.5]))
+            else:
+                t = 1.0 if rng.random() < 0.3 else rng.uniform(1, 1.3)
+            p = p.astype(np.float32).astype(np.float64)
+            a = rng.uniform(-np.pi, np.pi)
+            lat = np.rint(p + rng.uniform(1, 60 / t) * np.array([np.cos(a), np.sin(a)]))
+            q = (p + t * (lat - p)).astype(np.float32)
+            if exact:  # (multiples of 1 / 32 below 512: float32 holds them)
+                assert np.array_equal(q.astype(np.float64), p + t * (lat - p))
+            j = int(rng.integers(2))
+            q[j] = _ulps(q[j], rng.integers(-2, 3))
+        elif mode <= 7:
+            if mode == 7:
+                p = c + rng.integers(0, 2, 2)
+            a, ln = rng.uniform(-np.pi, np.pi), rng.uniform(1, 59)
+            q = np.rint(p + ln * np.array([np.cos(a), np.sin(a)]))
+        else:
+            if w > 501 and rng.random() < 0.8:
+                p[0] = rng.uniform(500, w)
+            if h > 501 and rng.random() < 0.8:
+                p[1] = rng.uniform(500, h)
+            q = p + rng.uniform(-0.7, 0.7, 2)
+            if mode == 9:  # an endpoint on a grid line
+                j = int(rng.integers(2))
+                q[j] = np.rint(q[j])
+        p, q = np.asarray(p, np.float32), np.asarray(q, np.float32)
+        d = q.astype(np.float64) - p.astype(np.float64)
+        if (np.array_equal(p, q) or np.hypot(d[0], d[1]) > 60 or (q < -3).any() or q[0] > w + 3 or q[1] > h + 3):
+            continue  # (drawn again: the classes stay what they are)
+        out[i] = np.concatenate([p, q])
+        i += 1
+    return out
+
+
+def make_scan_wide():
+    """lidar_scan_wide.npz: the reference's __lidar_scan over the GEOS model on five maps up to 511 wide or high, for
+    segments up to 60 long.  Pose group: K poses x B directions per map, q = p + dirs[b] in float32 (the form
+    lidar_scan_poses and lidar_scan_spread take); free group: near-lattice passes, lattice endpoints, short segments
+    at coordinates above 500."""
+    lmod = _lidar_module()
+    Env = lmod.LIDARLocalization2DEnv
+    FixedFloorMaps = fixed_floor_maps_dataset()
+    rng = np.random.default_rng(511)
+    out = {"map_hw": np.array([s[:2] for s in SCAN_WIDE_MAPS]), "pose_range": np.array(SCAN_WIDE_RANGE, np.float32)}
+    poses, dirs, pose_dist, free_mi, free_segs, free_dist = [], [], [], [], [], []
+    for mi, (h, w, noise, border) in enumerate(SCAN_WIDE_MAPS):
+        m = rng.random((h, w)) < noise
+        if border:
+            m[0, :] = m[-1, :] = m[:, 0] = m[:, -1] = True
+        out[f"map{mi}_bits"] = np.packbits(m, axis=-1)
+        # as make_lidar_scan: the map goes in through __set_map (here the constructor's own call for a static map);
+        # the scan does not depend on the env's range
+        env = Env(dataset=FixedFloorMaps(m[None]), static_map=True, lidar_beam_count=8, prefetch=False)
+        scan = env._LIDARLocalization2DEnv__lidar_scan
+        d = _scan_wide_dirs(rng)
+        ps = _scan_wide_poses(rng, m, border, SCAN_WIDE_POSES)
+        pd = np.zeros((len(ps), len(d)), np.float32)
+        for k, p in enumerate(ps):
+            q = p[None] + d
+            assert q.dtype == np.float32
+            pd[k] = scan(p, q)[0]
+        poses.append(ps), dirs.append(d), pose_dist.append(pd)
+        segs = _scan_wide_free(rng, m, border, SCAN_WIDE_FREE)
+        free_mi.append(np.full(len(segs), mi, np.int32))
+        free_segs.append(segs)
+        free_dist.append(np.array([scan(s[:2], s[None, 2:])[0][0] for s in segs], np.float32))
+        print("scan_wide map", mi, (h, w), "done")
+    save("lidar_scan_wide.npz", poses=np.stack(poses), dirs=np.stack(dirs), pose_distance=np.stack(pose_dist),
+         free_map_index=np.concatenate(free_mi), free_segments=np.concatenate(free_segs),
+         free_distance=np.concatenate(free_dist), **out)
+
+
+def make_lidar_long():
+    """LIDAR env traces at lidar_range 9.5 .. 60 over a pool of nine 72 x 72 maps (two words per row; square, because
+    the reference raises IndexError for H != W once a scan point leaves the map), 105 steps each."""
+    maps = fixed_floor_maps(n=9, h=72, w=72, seed=72)
+    ds, extra = fixed_floor_maps_dataset()(maps), pool_extra(maps)
+    run_lidar_env("pool72_r12_b12", ds, False, 12, 5, 105, 3, "wide", extra=extra, lidar_range=12)
+    run_lidar_env("pool72_r60_b12", ds, False, 12, 4, 105, 4, "wide", extra=extra, lidar_range=60)
+    run_lidar_env("pool72_static_r9p5_b16", ds, True, 16, 6, 105, 6, "wide", static_map_index=5, extra=extra,
+                  lidar_range=9.5)
+    run_lidar_env("pool72_r28_b8_grid", ds, False, 8, 5, 105, 8, "grid", extra=extra, lidar_range=28)
+
+
 SECTIONS = {"rng": make_rng, "maps": make_maps, "loss": make_loss, "scan": make_lidar_scan,
             "lidar": make_lidar_env, "lidar_beams": make_lidar_env_beams, "image": make_image_env,
             "sparse": make_sparse_env, "circle_square": make_circle_square,
             "light_dark": make_light_dark, "render": make_render, "hf": make_hf, "pool": make_pool,
-            "stream": make_stream}
+            "stream": make_stream, "scan_wide": make_scan_wide, "lidar_long": make_lidar_long}
 
 
 def main(argv):

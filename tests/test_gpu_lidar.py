@@ -29,8 +29,14 @@ ENV_CASES = {
     "pool48x40_b16": ("pool", 0, False, 16),
     "pool48x40_static_b8": ("pool", 0, True, 8),
     "pool36_open_b8": ("pool", 0, False, 8),
+    # nine 72 x 72 maps at the lidar_range the fixture stores (make_golden.make_lidar_long): 12 and 60 (the RowsGlobal
+    # step instance), 9.5 (the staged window, beam boxes taller than 8 rows), 28 on lattice and half-lattice positions
+    "pool72_r12_b12": ("pool", 0, False, 12),
+    "pool72_r60_b12": ("pool", 0, False, 12),
+    "pool72_static_r9p5_b16": ("pool", 0, True, 16),
+    "pool72_r28_b8_grid": ("pool", 0, False, 8),
 }
-POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index
+POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index (make_lidar_long's too)
 
 
 class UserFloorMaps:
@@ -63,6 +69,11 @@ class UserFloorMaps:
 def pool_maps(d) -> np.ndarray:
     h, w = (int(x) for x in d["pool_hw"])
     return np.unpackbits(d["pool_bits"], axis=-1)[..., :w].astype(bool).reshape(-1, h, w)
+
+
+def lidar_range_of(d) -> float:
+    """The lidar_range a trace was recorded at (fixtures without the entry: the reference's default)."""
+    return float(d["lidar_range"]) if "lidar_range" in d.files else 5.0
 
 
 def _ds(ap, kind, size, d=None):
@@ -208,6 +219,20 @@ def test_device_scan_matches_reference_model(gpu):
     assert set(np.unique(kinds)) == set(range(6))
 
 
+def test_device_scan_matches_reference_model_wide(gpu):
+    """Every segment of tests/golden/lidar_scan_wide.npz (maps up to 511 wide or high, segments up to 60 long, both
+    groups) against the reference's own __lidar_scan over the GEOS model."""
+    from test_oracle_golden import scan_wide
+
+    g = scan_wide()
+    for mi, m in enumerate(g.maps):
+        sel = g.map_index == mi
+        dist, _ = _scan_gpu(gpu, m[None], np.zeros(int(sel.sum()), np.int32), g.segments[sel])
+        want = g.distance[sel]
+        bad = np.nonzero(dist.view(np.int32) != want.view(np.int32))[0]
+        assert len(bad) == 0, (mi, len(bad), [(g.segments[sel][i], dist[i], want[i]) for i in bad[:5]])
+
+
 def test_device_scan_matches_oracle_degenerate_sweep(gpu, oracle_mod):
     """Random + lattice-aligned segments (corner touches, collinear runs) on 64x64 rooms and 127 mazes."""
     rng = np.random.default_rng(3)
@@ -297,8 +322,8 @@ def test_vector_env_matches_reference_trace(gpu, name):
     n = d["actions"].shape[1]
     sparse = name.endswith("_sparse")
     env = ap.LIDARLocalization2DVectorEnv(num_envs=n, dataset=_ds(ap, kind, size, d), static_map=static,
-                                          lidar_beam_count=beams, device=gpu, log_stats=True, sparse=sparse,
-                                          sparse_reset_info=sparse,
+                                          lidar_beam_count=beams, lidar_range=lidar_range_of(d), device=gpu,
+                                          log_stats=True, sparse=sparse, sparse_reset_info=sparse,
                                           static_map_index=POOL_STATIC_INDEX if kind == "pool" and static else 0)
     obs, info = env.reset(seed=int(d["seed"]))
     vec_off = 0

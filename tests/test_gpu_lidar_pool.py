@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from test_gpu_lidar import UserFloorMaps, pool_maps
+from test_gpu_lidar import POOL_STATIC_INDEX, UserFloorMaps, lidar_range_of, pool_maps
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +119,43 @@ def test_pool_static_map_matches_oracle(gpu, oracle_mod, backend):
         obs, rew, term, trunc, info = env.step({"action": a, "prediction": p})
         ref.step(to_np(a) if backend == "torch" else a, to_np(p) if backend == "torch" else p)
         _compare(env, ref, {k: to_np(v) for k, v in obs.items()}, to_np(rew), to_np(term), t, True)
+    env.close()
+
+
+@pytest.mark.parametrize("backend", ["numpy", "torch"])
+@pytest.mark.parametrize("name", ["pool72_r12_b12", "pool72_r60_b12", "pool72_static_r9p5_b16", "pool72_r28_b8_grid"])
+def test_long_range_pool_env_matches_reference_golden(gpu, name, backend):
+    """The reference env's own traces at lidar_range 9.5 .. 60 over nine 72 x 72 maps (tests/golden/lidar_env_pool72_*,
+    105 steps: one TimeLimit autoreset), on both backends; the env is built with the range the fixture stores."""
+    import torch
+
+    import ap_gym_amd as ap
+
+    d = golden(f"lidar_env_{name}.npz")
+    n, beams, static = d["actions"].shape[1], d["lidar"].shape[2], "static" in name
+    env = ap.LIDARLocalization2DVectorEnv(num_envs=n, dataset=UserFloorMaps(pool_maps(d)), static_map=static,
+                                          static_map_index=POOL_STATIC_INDEX if static else 0,
+                                          lidar_beam_count=beams, lidar_range=lidar_range_of(d), device=gpu,
+                                          array_backend=backend)
+    to_np = (lambda x: x.cpu().numpy()) if backend == "torch" else (lambda x: x)
+    obs, info = env.reset(seed=int(d["seed"]))
+    assert np.array_equal(to_np(obs["lidar"]), d["reset_lidar"])
+    assert np.array_equal(to_np(obs["odometry"]), d["reset_odometry"])
+    assert np.array_equal(to_np(info["map_idx"]), d["reset_map_idx"])
+    if not static:
+        assert np.array_equal(np.packbits(to_np(obs["map"])[..., 0] > 0, axis=-1), d["reset_map"])
+    for t in range(d["actions"].shape[0]):
+        a, p = d["actions"][t], d["predictions"][t]
+        if backend == "torch":
+            a, p = torch.as_tensor(a, device=gpu), torch.as_tensor(p, device=gpu)
+        obs, rew, term, trunc, info = env.step({"action": a, "prediction": p})
+        assert np.array_equal(to_np(obs["lidar"]), d["lidar"][t]), t
+        assert np.array_equal(to_np(obs["odometry"]), d["odometry"][t]), t
+        assert np.array_equal(to_np(obs["time_step"]), d["time_step"][t]), t
+        assert np.array_equal(to_np(rew), d["reward"][t]), t
+        assert np.array_equal(to_np(term), d["terminated"][t]), t
+        if not static:
+            assert np.array_equal(np.packbits(to_np(obs["map"])[..., 0] > 0, axis=-1), d["map"][t]), t
     env.close()
 
 

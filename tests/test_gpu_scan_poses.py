@@ -13,7 +13,8 @@ import pytest
 
 from test_gpu_lidar_pool import random_pool
 from test_map_bits_host import pack_bits_np
-from test_scan_poses_host import pose_scores_np, scan_poses_np
+from test_oracle_golden import scan_wide
+from test_scan_poses_host import normalize_np, pose_scores_np, scan_poses_np
 
 pytestmark = pytest.mark.gpu
 
@@ -374,6 +375,33 @@ def test_distances_equal_scan_batch(gpu, oracle_mod):
     dist, _ = _scan_gpu(gpu, maps, mi, segs)
     got = ap.lidar_scan_poses(dev_bits(maps, gpu), size, dev(poses, gpu), beams=beams, lidar_range=5, normalize=False)
     assert np.array_equal(raw(got).reshape(-1), raw(dist))
+
+
+# ------------------------------------------------------------------ 8b: against the reference's scan over the model
+@pytest.mark.parametrize("mi", range(5))
+def test_scans_and_scores_equal_the_reference_model_on_wide_maps(gpu, mi):
+    """The pose group of tests/golden/lidar_scan_wide.npz (maps up to 511 wide or high, directions 1..60 long, from
+    the fixture): distances, normalised values and scores against the reference's own __lidar_scan over the GEOS model
+    -- no oracle in between."""
+    import torch
+
+    import ap_gym_amd as ap
+
+    g = scan_wide()
+    m, want = g.maps[mi], g.pose_distance[mi][None]  # [1, K, B]
+    w, beams = m.shape[1], want.shape[2]
+    bits, poses, dirs = dev_bits(m[None], gpu), dev(g.poses[mi][None].copy(), gpu), dev(g.dirs[mi].copy(), gpu)
+    err = torch.zeros(1, dtype=torch.int32, device=gpu)
+    kw = dict(beams=beams, lidar_range=g.pose_range, beam_dirs=dirs, err=err)
+    got = ap.lidar_scan_poses(bits, w, poses, normalize=False, **kw)
+    assert got.shape == want.shape and np.array_equal(raw(got), raw(want))
+    norm = normalize_np(want, g.pose_range)
+    assert np.array_equal(raw(ap.lidar_scan_poses(bits, w, poses, normalize=True, **kw)), raw(norm))
+    obs = np.ascontiguousarray(norm[:, 0, :])  # pose 0's own scan
+    sc = ap.lidar_pose_scores(bits, w, poses, dev(obs, gpu), **kw).cpu().numpy()
+    assert np.array_equal(raw(sc), raw(pose_scores_np(norm, obs)))
+    assert sc[0, 0] == 0.0 and not np.signbit(sc[0, 0]) and (sc[0, 1:] > 0).any()
+    assert int(err.item()) == 0
 
 
 # ------------------------------------------------------------------ 9: the env's own observation

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from test_gpu_scan_poses import dev, dev_bits, host, oracle
+from test_oracle_golden import scan_wide
+from test_scan_poses_host import normalize_np
 from test_scan_spread_host import F, scan_spread_np
 
 pytestmark = pytest.mark.gpu
@@ -135,6 +137,29 @@ def test_spread_and_mean_equal_the_restatement_bit_for_bit(gpu, ci):
     assert not np.isnan(want["spread"]).any() and (k == 1 or (want["spread"] > 0).any())
     if k == 1:
         assert (want["spread"] == 0).all()
+
+
+@pytest.mark.parametrize("mi", range(5))
+def test_spread_equals_the_restatement_on_the_reference_models_scans(gpu, mi):
+    """The pose group of tests/golden/lidar_scan_wide.npz as two candidates of K / 2 hypotheses each, uniform weights:
+    the restatement is fed the reference's own scans over the GEOS model (the fixture's distances), not the kernel's
+    or the oracle's."""
+    import torch
+
+    import ap_gym_amd as ap
+
+    g = scan_wide()
+    m, dist = g.maps[mi], g.pose_distance[mi]
+    (k, beams), w = dist.shape, m.shape[1]
+    assert k % 2 == 0 and k // 2 <= 4096 and beams <= 1024
+    poses = g.poses[mi].reshape(1, 2, k // 2, 2).copy()  # (the shared fixture arrays are read-only)
+    weight = np.full((1, k // 2), 0.5, F)
+    want = scan_spread_np(normalize_np(dist, g.pose_range).reshape(1, 2, k // 2, beams), weight)
+    err = torch.zeros(1, dtype=torch.int32, device=gpu)
+    res = ap.lidar_scan_spread(dev_bits(m[None], gpu), w, dev(poses, gpu), dev(weight, gpu), beams=beams,
+                               lidar_range=g.pose_range, mean=True, err=err, beam_dirs=dev(g.dirs[mi].copy(), gpu))
+    assert same_values(res.spread, want["spread"]) and same_values(res.mean, want["mean"])
+    assert int(err.item()) == 0 and want["err"] == 0 and (want["spread"] > 0).all()
 
 
 def test_spread_alone_and_into_out(gpu):

@@ -83,6 +83,17 @@ def test_fast_call_module_reaches_the_c_abi():
         assert c_fn(ctypes.byref(cfg), ctypes.byref(st), None, None, *c_tail) == N.APG_E_INVALID
 
 
+def test_scan_batch_validates_on_the_host():
+    """apg_lidar_scan_batch takes the map sides the envs take (1..511; the 511-wide map of
+    tests/golden/lidar_scan_wide.npz runs through it on the GPU) and refuses anything else before any HIP call."""
+    from ap_gym_amd import _native as N
+
+    fn = N.lib().apg_lidar_scan_batch
+    for h, w, n in ((512, 64, 1), (64, 512, 1), (0, 64, 1), (64, 0, 1), (64, 64, 0), (511, 511, -1)):
+        assert fn(None, None, h, w, None, n, None, None, None) == N.APG_E_INVALID, (h, w, n)
+        assert N.lib().apg_last_error()
+
+
 def test_capi_validation_without_gpu():
     import ctypes
 

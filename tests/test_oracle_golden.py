@@ -3,9 +3,13 @@
 CPU only.  These pin the restatement before it is trusted as the checker of the HIP kernels:
   rng.npz        numpy 2.2.6 itself
   maps.npz       reference FloorMapDatasetRooms/Maze
-  lidar_scan.npz reference __lidar_scan + exact-rational GEOS model
+  lidar_scan.npz reference __lidar_scan + exact-rational GEOS model (lidar_scan_wide.npz: maps up to 511 wide or high,
+                 segments up to 60 long)
   lidar_env_*    reference LIDARLocalization2DEnv + TimeLimit + SyncVectorEnv composition
 """
+
+import functools
+import types
 
 import numpy as np
 import pytest
@@ -29,8 +33,19 @@ ENV_CASES = {
     "pool36_open_b8": ("pool", 0, False, 8),
     # a user FloorMapDataset of len 2**32, maps from default_rng(idx) (tests/stream_maps.py): fetched per draw
     "stream40_b16": ("stream", 0, False, 16),
+    # nine 72 x 72 maps (two words per row) at the lidar_range the fixture stores: 12 and 60 (scans over global rows),
+    # 9.5 (the staged window with beam boxes taller than 8 rows), 28 on lattice and half-lattice positions
+    "pool72_r12_b12": ("pool", 0, False, 12),
+    "pool72_r60_b12": ("pool", 0, False, 12),
+    "pool72_static_r9p5_b16": ("pool", 0, True, 16),
+    "pool72_r28_b8_grid": ("pool", 0, False, 8),
 }
-POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index
+POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index (make_lidar_long's too)
+
+
+def lidar_range_of(d) -> float:
+    """The lidar_range a trace was recorded at (fixtures without the entry: the reference's default)."""
+    return float(d["lidar_range"]) if "lidar_range" in d.files else 5.0
 
 
 def pool_maps(d) -> np.ndarray:
@@ -88,6 +103,54 @@ def test_scan_matches_reference_model(oracle_mod):
     assert (kinds > 0).all(), kinds
 
 
+@functools.lru_cache(maxsize=None)
+def scan_wide():
+    """lidar_scan_wide.npz, read once and shared (read-only) with the GPU tests: `maps` (five bool [H, W]), the pose
+    group (`poses` [5, K, 2], `dirs` [5, B, 2], `pose_distance` [5, K, B], `pose_range`) and every segment of both
+    groups (`segments` [N, 4], `map_index` [N], `distance` [N]; pose group first, q = p + dirs[b] in float32)."""
+    g = golden("lidar_scan_wide.npz")
+    maps = [np.unpackbits(g[f"map{i}_bits"], axis=-1)[:, :w].astype(bool) for i, (h, w) in enumerate(g["map_hw"])]
+    assert all(m.shape == tuple(hw) for m, hw in zip(maps, g["map_hw"]))
+    poses, dirs = g["poses"], g["dirs"]
+    n_maps, k, b = g["pose_distance"].shape
+    q = poses[:, :, None, :] + dirs[:, None, :, :]
+    assert q.dtype == np.float32 and q.shape == (n_maps, k, b, 2)
+    pose_segs = np.concatenate([np.broadcast_to(poses[:, :, None, :], q.shape), q], axis=-1).reshape(-1, 4)
+    out = types.SimpleNamespace(
+        maps=maps, poses=poses, dirs=dirs, pose_distance=g["pose_distance"], pose_range=float(g["pose_range"]),
+        segments=np.concatenate([pose_segs, g["free_segments"]]),
+        map_index=np.concatenate([np.repeat(np.arange(n_maps, dtype=np.int32), k * b), g["free_map_index"]]),
+        distance=np.concatenate([g["pose_distance"].reshape(-1), g["free_distance"]]))
+    for a in (*maps, poses, dirs, out.pose_distance, out.segments, out.map_index, out.distance):
+        a.setflags(write=False)
+    return out
+
+
+def test_scan_wide_matches_reference_model(oracle_mod):
+    """The oracle against the reference's __lidar_scan over the GEOS model, bit for bit, on every segment of both
+    groups; and the conditions the fixture has to meet to be worth its bytes."""
+    g = scan_wide()
+    n = len(g.distance)
+    assert n == len(g.segments) == len(g.map_index) and n >= 15000
+    occ = [m.astype(np.uint8) for m in g.maps]
+    got, kinds = np.zeros(n, np.float32), np.zeros(n, int)
+    for i, (mi, seg) in enumerate(zip(g.map_index, g.segments)):
+        got[i], kinds[i] = oracle_mod.lidar_scan(occ[mi], seg[:2], seg[2:])
+    bad = np.nonzero(got.view(np.int32) != g.distance.view(np.int32))[0]
+    assert len(bad) == 0, (len(bad), [(int(i), g.segments[i], got[i], g.distance[i]) for i in bad[:5]])
+    counts = np.bincount(kinds, minlength=6)
+    print("scan_wide:", n, "segments, result kinds (empty, line, multiline, point, multipoint, collection)", counts)
+    assert len(counts) == 6 and (counts >= 25).all(), counts
+    assert (counts[:3] >= 1000).all(), counts  # empty, LineString, MultiLineString
+    seg = g.segments.astype(np.float64)
+    assert (np.hypot(seg[:, 2] - seg[:, 0], seg[:, 3] - seg[:, 1]) > 30).sum() >= 2000
+    # a word boundary of the packed rows (a multiple of 64 inside the map) strictly inside the segment's x extent
+    lo, hi = np.minimum(seg[:, 0], seg[:, 2]), np.maximum(seg[:, 0], seg[:, 2])
+    first = 64 * np.maximum(np.floor(lo / 64) + 1, 1)
+    width = np.array([m.shape[1] for m in g.maps])[g.map_index]
+    assert ((first < hi) & (first < width)).sum() >= 1000
+
+
 @pytest.mark.parametrize("name", sorted(ENV_CASES))
 def test_vector_env_trace(oracle_mod, name):
     kind, size, static, beams = ENV_CASES[name]
@@ -96,7 +159,7 @@ def test_vector_env_trace(oracle_mod, name):
     sparse = name.endswith("_sparse")
     if kind == "pool":
         env = oracle_mod.OracleLidarVectorEnv(n, "pool", 0, static, POOL_STATIC_INDEX if static else 0, beams,
-                                              pool=pool_maps(d))
+                                              lidar_range=lidar_range_of(d), pool=pool_maps(d))
     elif kind == "stream":
         from stream_maps import STREAM_LEN, rng_floor_map
 

@@ -9,6 +9,12 @@ import numpy as np
 import pytest
 
 
+def normalize_np(dist, lidar_range):
+    """The divide-and-clip of write_obs (oracle/apg_oracle_lidar.c) in float32: distances in cells to the
+    observation's values."""
+    return np.clip(np.asarray(dist, np.float32) / np.float32(lidar_range), np.float32(-1), np.float32(1))
+
+
 def scan_poses_np(oracle, maps, poses, dirs, lidar_range, map_ids=None, normalize=True):
     """numpy restatement of apg_lidar_scan_poses' scan output.  maps: bool / uint8 [n_src, H, W]; poses float32
     [M, K, 2]; dirs float32 [B, 2].  Beam b of pose p is p -> (p + dirs[b]).astype(float32), scanned by the oracle's
@@ -21,7 +27,6 @@ def scan_poses_np(oracle, maps, poses, dirs, lidar_range, map_ids=None, normaliz
     m, k, _ = poses.shape
     ids = (np.zeros(m, np.int64) if n_src == 1 else np.arange(m)) if map_ids is None else np.asarray(map_ids)
     empty = np.zeros((h, w), np.uint8)
-    rng_f32 = np.float32(lidar_range)
     out = np.zeros((m, k, len(dirs)), np.float32)
     for i in range(m):
         occ = maps[ids[i]] if 0 <= ids[i] < n_src else empty
@@ -33,7 +38,7 @@ def scan_poses_np(oracle, maps, poses, dirs, lidar_range, map_ids=None, normaliz
             for b, d in enumerate(dirs):
                 q = (p + d).astype(np.float32)
                 dist = oracle.lidar_scan(occ, p, q)[0]
-                out[i, j, b] = np.clip(np.float32(dist) / rng_f32, np.float32(-1), np.float32(1)) if normalize else dist
+                out[i, j, b] = normalize_np(dist, lidar_range) if normalize else dist
     return out
 
 
