@@ -1737,6 +1737,27 @@ int glimpse_units_per_block(int per, int ppt_default = 4) {
   return std::max(1, std::min(GS_MAX_UNITS, (ppt * GS_THREADS + per - 1) / per));
 }
 
+// FastDiv::div(n) equals n / d for every n <= n_max exactly while n_max * (ceil(2^32 / d) * d - 2^32) < 2^32
+// (the struct's "n < 2^32 / d", in full; the worst n is the one with n % d == d - 1).
+bool fastdiv_exact(uint32_t d, uint64_t n_max) {
+  if (d <= 1) return true;
+  const uint64_t one = (uint64_t)1 << 32, m = (one + d - 1) / d;
+  return n_max * (m * d - one) < one;
+}
+
+// The units per workgroup lowered until every reciprocal division of gs_axes / gs_pixels_t is exact: q < upb * per
+// by per, pix < per by s1, q < upb * side by side.  One unit always is (per <= 2^16); from per = 46805 (185 x 253)
+// up two units mostly are not, and a wrong unit index reads LDS and the pool out of bounds.  validate() admits
+// glimpses of up to MAX_PW_N = 16384 values today, where every choice below is exact (tests/test_host.py sweeps
+// all sensors up to GS_MAX_SIDE): this keeps the kernels' own limit, GS_MAX_SIDE, safe should that bound rise.
+int fastdiv_safe_units(int upb, int s0, int s1) {
+  const uint64_t per = (uint64_t)s0 * s1, side = (uint64_t)s0 + s1;
+  while (upb > 1 && !(fastdiv_exact((uint32_t)per, upb * per - 1) && fastdiv_exact((uint32_t)s1, per - 1) &&
+                      fastdiv_exact((uint32_t)side, upb * side - 1)))
+    upb--;
+  return upb;
+}
+
 template <class PosT>
 int launch_glimpse(const GlimpseGeo &g, const void *pool, const int64_t *index, const PosT *pos, int n, int npos,
                    float *out, uint32_t *err, hipStream_t s) {
@@ -1745,7 +1766,7 @@ int launch_glimpse(const GlimpseGeo &g, const void *pool, const int64_t *index, 
   static const bool generic = getenv("APG_GLIMPSE_GENERIC") != nullptr;
   if (g.s0 <= GS_MAX_SIDE && g.s1 <= GS_MAX_SIDE && !generic) {
     const int per = g.s0 * g.s1, units = n * npos;
-    const int upb = glimpse_units_per_block(per);
+    const int upb = fastdiv_safe_units(glimpse_units_per_block(per), g.s0, g.s1);
     const size_t dyn = (size_t)upb * (g.s0 + g.s1) * sizeof(Axis);
     hipLaunchKernelGGL(k_glimpse_sep<PosT>, dim3(grid_for(units, upb)), dim3(GS_THREADS), dyn, s, g, pool, index, pos,
                        npos, units, upb, make_fastdiv((uint32_t)per), make_fastdiv((uint32_t)g.s1),
@@ -2055,6 +2076,7 @@ int apg_image_step(const apg_image_config *c, const apg_image_state *st, const f
         upb = std::min(ENV_WAVE, (int)(((int64_t)n + (int64_t)whole * resident - 1) / ((int64_t)whole * resident)));
       }
     }
+    upb = fastdiv_safe_units(upb, g.s0, g.s1);  // the re-choice can make 1 into 2 whatever the sensor size
     size_t dyn = (size_t)upb * (g.s0 + g.s1) * sizeof(Axis);
     if (c->kind == APG_IMAGE_CLASSIFY) dyn += (size_t)upb * (c->num_classes + 2) * sizeof(float);
     const dim3 grid(grid_for(n, upb)), block(GS_THREADS);

@@ -16,7 +16,8 @@ Sources of truth, per fixture:
                    (lidar_env_pool72_*: at lidar_range 9.5 .. 60, which the fixture stores).
   image_*.npz      the reference's ImageClassificationVectorEnv / ImageLocalizationVectorEnv
                    (ImagePerceptionModule, scipy RegularGridInterpolator, CE/MSE losses) run as-is on
-                   small synthetic uint8 pools (HF datasets are not available offline), seeded through
+                   small synthetic uint8 pools (image_cls_f32rgb, image_loc_f64gray3: float pools in
+                   [-0.2, 1.2]; HF datasets are not available offline), seeded through
                    the gymnasium VectorEnv.reset restatement in tests/golden/_stubs.
 The fixtures hold data only (inputs and expected outputs).  See DESIGN.md §Oracle for what each pins.
 """
@@ -384,10 +385,13 @@ def _image_modules():
 
 
 def run_image_env(name, kind, pool_shape, channels, num_classes, sensor, scale, step_limit, invert, n_envs,
-                  steps, seed, pool_len, pool_seed, sparse=False):
+                  steps, seed, pool_len, pool_seed, sparse=False, pool_dtype=np.uint8, pool_range=(-0.2, 1.2)):
     ipm, icd, ic, il = _image_modules()
     prng = np.random.default_rng(pool_seed)
-    pool = prng.integers(0, 256, (pool_len, *pool_shape), dtype=np.uint8)
+    if pool_dtype == np.uint8:
+        pool = prng.integers(0, 256, (pool_len, *pool_shape), dtype=np.uint8)
+    else:  # any other dtype is cast to float32 without the / 255 (image_classification_dataset.py:66-70)
+        pool = prng.uniform(*pool_range, (pool_len, *pool_shape)).astype(pool_dtype)
     # smooth a little so glimpses differ in structured ways (ties in uniqueness are rare either way)
     labels = prng.integers(0, num_classes, pool_len).astype(np.int64)
 
@@ -483,6 +487,16 @@ def make_image_env():
     run_image_env("loc_mnist", "loc", (28, 28), 1, 10, (5, 5), 1.0, 16, False, 6, 40, 1, 30, 103)
     run_image_env("loc_tin12", "loc", (64, 64, 3), 3, 200, (12, 12), 1.0, 16, False, 2, 20, 4, 6, 104)
     run_image_env("loc_rect", "loc", (24, 20, 3), 3, 5, (4, 4), 1.25, 6, False, 4, 16, 9, 10, 105)
+    make_image_float_env()
+
+
+def make_image_float_env():
+    """Pools that are not uint8 (section "image_float" writes these two alone): a float32 RGB pool with values
+    below 0 and above 1 (both clips of get_glimpse), and a float64 grey pool shown with 3 channels."""
+    run_image_env("cls_f32rgb", "cls", (24, 20, 3), 3, 5, (4, 4), 1.25, 6, True, 4, 16, 6, 12, 106,
+                  pool_dtype=np.float32)
+    run_image_env("loc_f64gray3", "loc", (20, 24), 3, 4, (5, 5), 1.5, 8, False, 6, 20, 7, 12, 107,
+                  pool_dtype=np.float64)
 
 
 def make_sparse_env():
@@ -1048,7 +1062,8 @@ SECTIONS = {"rng": make_rng, "maps": make_maps, "loss": make_loss, "scan": make_
             "lidar": make_lidar_env, "lidar_beams": make_lidar_env_beams, "image": make_image_env,
             "sparse": make_sparse_env, "circle_square": make_circle_square,
             "light_dark": make_light_dark, "render": make_render, "hf": make_hf, "pool": make_pool,
-            "stream": make_stream, "scan_wide": make_scan_wide, "lidar_long": make_lidar_long}
+            "stream": make_stream, "scan_wide": make_scan_wide, "lidar_long": make_lidar_long,
+            "image_float": make_image_float_env}
 
 
 def main(argv):

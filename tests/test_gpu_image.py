@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 CE_RTOL = 0.0  # (bit-exact: numpy's float32 exp / log restated on the device)
 CE_ATOL = 0.0
 GOLDEN_CASES = ["cls_mnist", "cls_tin", "cls_gray3_rect", "loc_mnist", "loc_tin12", "loc_rect",
-                "cls_mnist_sparse", "loc_rect_sparse"]  # *_sparse: the "-sparse" ids (SparsifyVectorWrapper)
+                "cls_mnist_sparse", "loc_rect_sparse",  # *_sparse: the "-sparse" ids (SparsifyVectorWrapper)
+                "cls_f32rgb", "loc_f64gray3"]  # float32 RGB and float64 grey-as-RGB pools in [-0.2, 1.2]
 
 
 def _state_from_numpy(gen: np.random.Generator):
@@ -189,13 +190,32 @@ def test_glimpse_out_of_bounds_flags_like_scipy(gpu):
 
 
 # L = G*G*C: 25 and 108 (one leaf of numpy's pairwise sum), 432 (4 leaves), 300 (leaf tail), 4 (a leaf
-# shorter than 8), 768 (deeper combine stack); knobs: the generic kernel, and few workgroups (env striding)
-@pytest.mark.parametrize("h,w,c,sensor,n,knob", [(28, 28, 1, (5, 5), 24, None), (32, 32, 3, (6, 6), 6, None),
-                                                 (64, 64, 3, (12, 12), 2, None), (32, 32, 3, (10, 10), 4, None),
-                                                 (16, 16, 1, (2, 2), 3, None), (64, 64, 3, (16, 16), 2, None),
-                                                 (64, 64, 3, (12, 12), 2, "APG_UNIQUE_GENERIC=1"),
-                                                 (28, 28, 1, (5, 5), 24, "APG_UNIQUE_GRID=5")])
-def test_unique_top_k_matches_oracle(gpu, h, w, c, sensor, n, knob, monkeypatch):
+# shorter than 8), 768 (deeper combine stack); knobs: the generic kernel, and few workgroups (env striding).
+# Then float32 pools (the sampler reaches them through glimpse_pixel / pool_value: both clips, no / 255) and grey
+# pools shown as RGB (L triples: 48 instead of 16, another leaf plan).
+# (h, w, pool channels, obs channels, pool dtype, sensor, n, knob, tied); the first rows keep their earlier ids.
+# tied: the 2 x 2 row (L = 4, u8) has exactly equal values among each env's 11 largest; the oracle orders those by
+# index and so, as it happens, does the kernel: that row stays as it was, every other row must be free of such ties
+UNIQUE_CASES = [
+    pytest.param(28, 28, 1, 1, np.uint8, (5, 5), 24, None, False, id="28-28-1-sensor0-24-None"),
+    pytest.param(32, 32, 3, 3, np.uint8, (6, 6), 6, None, False, id="32-32-3-sensor1-6-None"),
+    pytest.param(64, 64, 3, 3, np.uint8, (12, 12), 2, None, False, id="64-64-3-sensor2-2-None"),
+    pytest.param(32, 32, 3, 3, np.uint8, (10, 10), 4, None, False, id="32-32-3-sensor3-4-None"),
+    pytest.param(16, 16, 1, 1, np.uint8, (2, 2), 3, None, True, id="16-16-1-sensor4-3-None"),
+    pytest.param(64, 64, 3, 3, np.uint8, (16, 16), 2, None, False, id="64-64-3-sensor5-2-None"),
+    pytest.param(64, 64, 3, 3, np.uint8, (12, 12), 2, "APG_UNIQUE_GENERIC=1", False,
+                 id="64-64-3-sensor6-2-APG_UNIQUE_GENERIC=1"),
+    pytest.param(28, 28, 1, 1, np.uint8, (5, 5), 24, "APG_UNIQUE_GRID=5", False,
+                 id="28-28-1-sensor7-24-APG_UNIQUE_GRID=5"),
+    pytest.param(24, 24, 3, 3, np.float32, (6, 6), 6, None, False, id="f32-24-24-rgb-6x6"),
+    pytest.param(20, 24, 1, 1, np.float32, (5, 5), 6, None, False, id="f32-20-24-grey-5x5"),
+    pytest.param(20, 24, 1, 3, np.float32, (4, 4), 6, None, False, id="f32-20-24-grey-as-rgb-4x4"),
+    pytest.param(20, 24, 1, 3, np.uint8, (4, 4), 6, None, False, id="u8-20-24-grey-as-rgb-4x4"),
+]
+
+
+@pytest.mark.parametrize("h,w,pc,c,dtype,sensor,n,knob,tied", UNIQUE_CASES)
+def test_unique_top_k_matches_oracle(gpu, h, w, pc, c, dtype, sensor, n, knob, tied, monkeypatch):
     import torch
 
     if knob:
@@ -206,13 +226,17 @@ def test_unique_top_k_matches_oracle(gpu, h, w, c, sensor, n, knob, monkeypatch)
     from oracle import image_oracle as io
 
     rng = np.random.default_rng(h + n)
-    pool = _pool(rng, n, h, w, c, np.uint8)
+    pool = _pool(rng, n, h, w, pc, dtype)
     index = np.arange(n)
     grid, cell = unique_sampling_grid((h, w), sensor, 1.0)
     top, g_grid, g_cell, u = io.unique_top_k(io.images_f32(pool, c), sensor, 1.0, 10)
     assert np.array_equal(grid, g_grid) and np.array_equal(cell, g_cell)
+    # the order of exactly tied values is pinned nowhere: the ranking compared below must not hold a tie (the 10
+    # chosen and the first one left out, pairwise distinct)
+    lead = -np.sort(-u, axis=-1)[:, :11]
+    assert lead.shape[1] == 11 and bool((np.diff(lead, axis=-1) < 0).all()) != tied
     p = grid.shape[0]
-    cfg = _cfg(N, n, N.APG_IMAGE_LOCALIZE, h, w, c, c, sensor, 1.0, np.uint8, n, top_k=10, points=p)
+    cfg = _cfg(N, n, N.APG_IMAGE_LOCALIZE, h, w, pc, c, sensor, 1.0, dtype, n, top_k=10, points=p)
     top_d = torch.zeros((n, 10), dtype=torch.int32, device=gpu)
     uniq = torch.zeros((n, p), dtype=torch.float32, device=gpu)
     keep = [_dev_pool(pool, gpu)] + [torch.as_tensor(x, device=gpu) for x in (index, grid)]
@@ -362,28 +386,119 @@ def test_image_env_box_staging_edges(gpu, kind, n, shape, sensor, k, steps, scal
     _env_vs_oracle(kind, n, shape, sensor, k, steps, scale)
 
 
-def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0):
+# Pool format x channels x env features, each at a ragged multi-workgroup N (the fused step holds up to 64 envs per
+# workgroup), 2 * step_limit + 3 steps.  The fused instances k_image_step_fused<kind, F32, PC, C> each row pins:
+# (kind, pool shape, pool dtype, obs channels, sensor, scale, K, N, step_limit, invert, log_stats, sparse)
+MATRIX_CASES = [
+    pytest.param("loc", (17, 19), np.float32, 1, (5, 5), 2.0, 10, 130, 5, False, True, False, id="loc-f32-1to1"),
+    pytest.param("loc", (20, 24), np.float32, 3, (4, 4), 1.25, 10, 193, 7, False, True, True, id="loc-f32-1to3"),
+    pytest.param("loc", (24, 20, 3), np.float32, 3, (6, 6), 1.0, 10, 131, 11, False, True, False, id="loc-f32-3to3"),
+    pytest.param("loc", (20, 24), np.uint8, 3, (5, 5), 1.5, 10, 193, 8, False, False, False, id="loc-u8-1to3"),
+    pytest.param("cls", (28, 28), np.float32, 1, (5, 5), 1.0, 10, 2000, 16, True, True, False, id="cls-f32-1to1"),
+    pytest.param("cls", (20, 24), np.float32, 3, (5, 5), 1.5, 4, 300, 8, True, False, False, id="cls-f32-1to3"),
+    pytest.param("cls", (33, 29, 3), np.float32, 3, (6, 6), 1.7, 13, 257, 20, False, True, False, id="cls-f32-3to3"),
+    # K = 17 is past CLS1_MAX_K: the unfused step (k_glimpse_sep with packed pitch, then k_image_env_cls)
+    pytest.param("cls", (33, 29, 3), np.float32, 3, (6, 6), 1.7, 17, 300, 5, False, True, False,
+                 id="cls-f32-3to3-k17-unfused"),
+    pytest.param("cls", (20, 24), np.uint8, 3, (5, 5), 1.5, 5, 300, 11, True, True, True, id="cls-u8-1to3"),
+    pytest.param("cls", (28, 28), np.uint8, 1, (5, 5), 1.0, 10, 300, 7, False, True, True, id="cls-u8-1to1"),
+]
+
+
+@pytest.mark.parametrize("kind,shape,dtype,obs_c,sensor,scale,k,n,limit,invert,log_stats,sparse", MATRIX_CASES)
+def test_image_env_pool_format_feature_matrix(gpu, kind, shape, dtype, obs_c, sensor, scale, k, n, limit, invert,
+                                              log_stats, sparse):
+    """Float32 pools (both clips of the glimpse, no / 255, no pool padding), grey pools shown as RGB, label
+    inversion, the log wrapper's statistics and the sparse wrapper against the oracle, bit for bit, across two batch
+    autoresets (the draws made ahead and folded into the fused step)."""
+    from ap_gym_amd import _native as N
+
+    _env_vs_oracle(kind, n, shape, sensor, k, 2 * limit + 3, scale, dtype=dtype, obs_c=obs_c, invert=invert,
+                   log_stats=log_stats, sparse=sparse, step_limit=limit,
+                   pool_format=N.APG_POOL_U8 if dtype == np.uint8 else N.APG_POOL_F32)
+
+
+@pytest.mark.parametrize("kind,shape,sensor,scale,k,n,limit", [("loc", (24, 20, 3), (6, 6), 1.0, 10, 131, 6),
+                                                                ("cls", (33, 29, 3), (6, 6), 1.7, 13, 257, 9)])
+def test_image_env_row_major_rgb_matches_oracle(gpu, monkeypatch, kind, shape, sensor, scale, k, n, limit):
+    """RGB u8 pools kept row-major (APG_IMAGE_TILED=0; tiled RGBX is the default): the fused step's u8 (3, 3)
+    instances against the oracle themselves, not only through the tiled env."""
+    from ap_gym_amd import _native as N
+
+    monkeypatch.setenv("APG_IMAGE_TILED", "0")
+    _env_vs_oracle(kind, n, shape, sensor, k, 2 * limit + 3, scale, log_stats=True, step_limit=limit,
+                   pool_format=N.APG_POOL_U8)
+
+
+def _assert_stats_equal(got, want, n, where):
+    """info["stats"] of the env against the oracle's _log: every scalar and its mask (value and dtype), every vector
+    as a list of np.float32 per env, first_correct / last_incorrect and their masks."""
+    assert set(got) == set(want) == {"scalar", "_scalar", "vector", "_vector"}, where
+    for m in ("_scalar", "_vector"):
+        assert np.asarray(got[m]).dtype == np.bool_ and np.array_equal(got[m], want[m]), (where, m)
+    assert set(got["scalar"]) == set(want["scalar"]), where
+    for key, w in want["scalar"].items():
+        g = np.asarray(got["scalar"][key])
+        assert g.dtype == w.dtype and g.shape == (n,), (where, key, g.dtype, w.dtype)
+        assert np.array_equal(g, w, equal_nan=w.dtype.kind == "f"), (where, key)
+    assert set(got["vector"]) == set(want["vector"]), where
+    for key, w in want["vector"].items():
+        g = got["vector"][key]
+        if key.startswith("_"):
+            assert np.asarray(g).dtype == np.bool_ and np.array_equal(g, w), (where, key)
+            continue
+        assert g.dtype == object and g.shape == w.shape == (n,), (where, key)
+        for i in range(n):
+            assert isinstance(g[i], list) and len(g[i]) == len(w[i]), (where, key, i)
+            assert all(type(x) is np.float32 for x in g[i]) and all(type(x) is np.float32 for x in w[i]), (where, key, i)
+        assert np.array_equal(np.array(list(g), np.float32), np.array(list(w), np.float32)), (where, key)
+
+
+def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0, dtype=np.uint8, obs_c=None, invert=False,
+                   log_stats=False, sparse=False, step_limit=16, pool_format=None):
     import ap_gym_amd as ap
     from oracle import image_oracle as io
 
     rng = np.random.default_rng(n)
-    pool = rng.integers(0, 256, (300, *shape), dtype=np.uint8)
+    if dtype == np.uint8:
+        pool = rng.integers(0, 256, (300, *shape), dtype=np.uint8)
+    else:
+        pool = rng.uniform(-0.2, 1.2, (300, *shape)).astype(dtype)
     labels = rng.integers(0, k, 300)
-    c = 1 if len(shape) == 2 else shape[-1]
+    c = obs_c or (1 if len(shape) == 2 else shape[-1])
     ds = ap.ArrayImageClassificationDataset(pool, labels, k, c)
-    cfg = ap.ImagePerceptionConfig(dataset=ds, sensor_size=sensor, sensor_scale=scale, step_limit=16)
-    env = (ap.ImageClassificationVectorEnv if kind == "cls" else ap.ImageLocalizationVectorEnv)(n, cfg)
-    ref = io.ImageVectorEnvOracle(kind, pool, labels, k, c, n, sensor, scale, 16)
+    cfg = ap.ImagePerceptionConfig(dataset=ds, sensor_size=sensor, sensor_scale=scale, step_limit=step_limit,
+                                   randomly_invert_labels=invert)
+    env = (ap.ImageClassificationVectorEnv if kind == "cls" else ap.ImageLocalizationVectorEnv)(
+        n, cfg, log_stats=log_stats, sparse=sparse)
+    assert pool_format is None or env._cfg.pool_dtype == pool_format  # the kernel instance the case is meant for
+    ref = io.ImageVectorEnvOracle(kind, pool, labels, k, c, n, sensor, scale, step_limit, invert=invert,
+                                  log_stats=log_stats, sparse=sparse)
     obs, info = env.reset(seed=11)
     robs, rinfo = ref.reset(11)
+    assert set(obs) == set(robs)
     for key in robs:
         assert np.array_equal(obs[key], robs[key]), key
+    assert np.array_equal(info["index"], rinfo["index"])
+    # what the oracle saw, for the conditions on the inputs below
+    counts = np.zeros(3, np.int64)  # glimpse values equal to 0, equal to 1, strictly between
+    batches, stats_steps, weights = [], 0, set()
+
+    def saw(o):
+        gl = o["glimpse"]
+        counts[:] += [(gl == 0).sum(), (gl == 1).sum(), ((gl > 0) & (gl < 1)).sum()]
+        if invert and ref.t == 0:  # a batch just drawn
+            batches.append((bool(ref.inverted.any()), bool((~ref.inverted).any())))
+
+    saw(robs)
     arng = np.random.default_rng(3)
     for t in range(steps):
         a = arng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
         p = (arng.standard_normal((n, k)) if kind == "cls" else arng.uniform(-1, 1, (n, 2))).astype(np.float32)
         got = env.step({"action": a, "prediction": p})
         want = ref.step(a, p)
+        saw(want[0])
+        assert set(got[0]) == set(want[0]), t
         for key in want[0]:
             assert np.array_equal(got[0][key], want[0][key]), (t, key)
         for i, name in ((1, "reward"), (2, "terminated"), (3, "truncated")):
@@ -391,10 +506,87 @@ def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0):
         gi, wi = got[4], want[4]
         assert np.array_equal(gi["index"], wi["index"])
         _assert_field("base_reward", gi["base_reward"], wi["base_reward"], wi["base_reward"].dtype, False)
-        _assert_field("target", gi["prediction"]["target"], wi["prediction"]["target"],
-                      np.asarray(wi["prediction"]["target"]).dtype, False)
+        g_tgt, w_tgt = gi["prediction"]["target"], wi["prediction"]["target"]
+        if sparse:  # SparsifyVectorWrapper: the target with its loss weight
+            assert set(g_tgt) == set(w_tgt) == {"target", "weight"}, t
+            _assert_field("weight", g_tgt["weight"], w_tgt["weight"], w_tgt["weight"].dtype, False)
+            weights.update(np.unique(w_tgt["weight"]).tolist())
+            g_tgt, w_tgt = g_tgt["target"], w_tgt["target"]
+        _assert_field("target", g_tgt, w_tgt, np.asarray(w_tgt).dtype, False)
         _assert_field("loss", gi["prediction"]["loss"], wi["prediction"]["loss"], wi["prediction"]["loss"].dtype,
                       kind == "cls")
+        assert ("stats" in gi) == ("stats" in wi), t
+        if "stats" in wi:
+            stats_steps += 1
+            _assert_stats_equal(gi["stats"], wi["stats"], n, t)
+    env.close()
+    # inputs that cannot tell a right kernel from a wrong one are worth nothing: checked on the oracle's side
+    if dtype != np.uint8:  # both clips of the float glimpse and its interior
+        assert (counts >= 0.01 * counts.sum()).all(), counts / counts.sum()
+    if invert:  # every batch drawn holds inverted and non-inverted envs
+        assert len(batches) == 1 + steps // (step_limit + 1) and all(a and b for a, b in batches), batches
+    if log_stats and steps > 2 * step_limit:
+        assert stats_steps >= 2
+    if sparse and steps > step_limit:
+        assert weights == {0.0, 1.0}
+
+
+def test_fused_step_largest_sensor_units_per_workgroup(gpu):
+    """The fused step's re-choice of the units per workgroup for whole generations makes 1 unit into 2 at
+    N = 4 * CUs + 1 whatever the sensor size, and the reciprocal division of the pixel index by s0 * s1 is exact for
+    two units only up to s0 * s1 = 46804 (tests/test_host.py restates the arithmetic and the host's guard,
+    fastdiv_safe_units).  Glimpses of more than 16384 values are refused on the host before any launch, a 255 x 255
+    sensor among them; at the largest square sensor admitted that is no power of two, 127 x 127, every glimpse of
+    the two-unit workgroups equals the standalone glimpse op at the env's position (one unit per workgroup), and the
+    oracle's for the first and last envs."""
+    import torch
+
+    import ap_gym_amd as ap
+    from ap_gym_amd import _native as N
+    from oracle import image_oracle as io
+
+    h = w = 256
+    k = 2
+    n = 4 * torch.cuda.get_device_properties(gpu).multi_processor_count + 1
+    rng = np.random.default_rng(8)
+    pool = rng.integers(0, 256, (2, h, w), dtype=np.uint8)
+    ds = ap.ArrayImageClassificationDataset(pool, np.array([0, 1]), k, 1)
+    big = ap.ImageClassificationVectorEnv(
+        2, ap.ImagePerceptionConfig(dataset=ds, sensor_size=(255, 255), sensor_scale=1.0), array_backend="torch")
+    with pytest.raises(ValueError, match="glimpse too large"):
+        big.reset(seed=1)
+    big.close()
+    sensor = (127, 127)
+    cfg = ap.ImagePerceptionConfig(dataset=ds, sensor_size=sensor, sensor_scale=1.0)
+    env = ap.ImageClassificationVectorEnv(n, cfg, array_backend="torch")
+    gcfg = _cfg(N, n, N.APG_IMAGE_CLASSIFY, h, w, 1, 1, sensor, 1.0, np.uint8, 2, k=k)
+    pool_t = _dev_pool(pool[..., None], gpu)
+    want = torch.zeros((n, 1, *sensor, 1), dtype=torch.float32, device=gpu)
+    err = torch.zeros(1, dtype=torch.int32, device=gpu)
+    images = io.images_f32(pool, 1)
+    sel = np.array([0, 1, n - 2, n - 1])
+
+    def check(obs, info, what):
+        pos = env._t["pos"]
+        assert pos.dtype == torch.float64 and pos.shape == (n, 2)
+        index = info["index"].to(torch.int64).contiguous()
+        N.check(N.lib().apg_image_glimpse(ctypes.byref(gcfg), N.ptr(pool_t), N.ptr(index), N.ptr(pos), 0, 1,
+                                          N.ptr(want), N.ptr(err), N.stream_handle(gpu)))
+        assert obs["glimpse"].shape == (n, *sensor, 1)
+        assert torch.equal(obs["glimpse"], want[:, 0]), what
+        ref = io.glimpse(images[index.cpu().numpy()[sel]], pos.cpu().numpy()[sel], sensor, 1.0)
+        assert np.array_equal(obs["glimpse"][torch.as_tensor(sel, device=gpu)].cpu().numpy(), ref), what
+
+    obs, info = env.reset(seed=1)
+    check(obs, info, "reset")
+    g = torch.Generator(device=gpu).manual_seed(2)
+    for t in range(3):
+        a = torch.rand((n, 2), generator=g, device=gpu) * 3 - 1.5
+        p = torch.randn((n, k), generator=g, device=gpu)
+        obs, rew, term, trunc, info = env.step({"action": a, "prediction": p})
+        check(obs, info, f"step {t}")
+    assert int(err.item()) == 0
+    env.check_errors()
     env.close()
 
 

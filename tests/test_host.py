@@ -733,3 +733,133 @@ def test_tiled_rgb_pool_layout(h, w):
     for ch in range(3):
         assert np.array_equal(b[off + ch], pool[..., ch])
     assert not b[off + 3].any()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float16, np.int16, np.bool_])
+@pytest.mark.parametrize("shape", [(7, 6, 5), (7, 6, 5, 1), (7, 6, 5, 3)])
+def test_array_dataset_pool_dtypes_cast_without_scaling(dtype, shape):
+    """_process_imgs_np (image_classification_dataset.py:66-70) divides uint8 images by 255 and only casts every other
+    dtype to float32: device_pool() hands the envs astype(float32) of the input exactly (values outside [0, 1]
+    included), a 3-D grey input with its channel axis added; get_data_point_batch() gives the same values."""
+    import ap_gym_amd as ap
+
+    rng = np.random.default_rng(len(shape))
+    if dtype is np.bool_:
+        data = rng.integers(0, 2, shape).astype(bool)
+    elif dtype is np.int16:
+        data = rng.integers(-300, 300, shape).astype(np.int16)
+    else:
+        data = rng.uniform(-0.2, 1.2, shape).astype(dtype)
+    labels = np.arange(shape[0]) % 3
+    ds = ap.ArrayImageClassificationDataset(data, labels, 3)
+    imgs, lab = ds.device_pool()
+    want = data.astype(np.float32)
+    want = want if want.ndim == 4 else want[..., None]
+    assert imgs.dtype == np.float32 and imgs.shape == want.shape and imgs.flags.c_contiguous
+    assert np.array_equal(imgs, want)
+    assert lab.dtype == np.int32 and np.array_equal(lab, labels)
+    assert ds.num_channels == want.shape[-1]
+    batch, _ = ds.get_data_point_batch(np.arange(shape[0]))
+    assert batch.dtype == np.float32 and np.array_equal(batch, want)
+    # the same pool through the dataset base class (a dataset that only implements the reference interface)
+    base = ap.image_dataset.ImageClassificationDataset.device_pool(ds)
+    assert base[0].dtype == np.float32 and np.array_equal(base[0], want)
+    if want.shape[-1] == 1:  # grey shown as RGB: the pool stays grey, the data points repeat the channel
+        ds3 = ap.ArrayImageClassificationDataset(data, labels, 3, 3)
+        assert np.array_equal(ds3.device_pool()[0], want)
+        assert np.array_equal(ds3.get_data_point_batch(np.arange(shape[0]))[0], np.repeat(want, 3, axis=-1))
+
+
+@pytest.mark.parametrize("shape", [(7, 6, 5), (7, 6, 5, 3)])
+def test_array_dataset_u8_pool_stays_u8(shape):
+    import ap_gym_amd as ap
+
+    data = np.random.default_rng(1).integers(0, 256, shape, dtype=np.uint8)
+    ds = ap.ArrayImageClassificationDataset(data, np.zeros(shape[0], np.int64), 2)
+    imgs, _ = ds.device_pool()
+    assert imgs.dtype == np.uint8 and np.array_equal(imgs, data if data.ndim == 4 else data[..., None])
+    batch, _ = ds.get_data_point_batch(np.arange(shape[0]))
+    assert batch.dtype == np.float32 and np.array_equal(batch, imgs.astype(np.float32) / 255)
+
+
+# apg_image.hip's reciprocal division and units-per-workgroup choices, restated
+def _fastdiv_m(d):
+    return 0 if d <= 1 else (2**32 + d - 1) // d  # make_fastdiv
+
+
+def _fastdiv_div(n, d):
+    return n if d == 1 else (n * _fastdiv_m(d)) >> 32  # FastDiv::div: __umulhi(n, m)
+
+
+def _fastdiv_exact(d, n_max):
+    return d <= 1 or n_max * (_fastdiv_m(d) * d - 2**32) < 2**32  # fastdiv_exact
+
+
+def _units_per_block(per, ppt=4):
+    return max(1, min(128, (ppt * 256 + per - 1) // per))  # glimpse_units_per_block (GS_MAX_UNITS, GS_THREADS)
+
+
+def _safe_units(upb, s0, s1):
+    per, side = s0 * s1, s0 + s1  # fastdiv_safe_units
+    while upb > 1 and not (_fastdiv_exact(per, upb * per - 1) and _fastdiv_exact(s1, per - 1)
+                           and _fastdiv_exact(side, upb * side - 1)):
+        upb -= 1
+    return upb
+
+
+def _fused_units(upb0, n, resident):
+    """apg_image_step's re-choice for whole generations (ENV_WAVE = 64), vectorised over n."""
+    gens = n / (upb0 * resident)
+    whole = np.maximum(1, np.floor(gens + 0.5).astype(np.int64))  # lround of a positive value
+    again = np.minimum(64, (n + whole * resident - 1) // (whole * resident))
+    return np.where(gens >= 1.0, again, upb0)
+
+
+def _fastdiv_all_exact(d, n_max):
+    """Every n <= n_max, divided as the device does (uint32 n, uint32 m, the high word of the product)."""
+    n = np.arange(n_max + 1, dtype=np.uint64)
+    return np.array_equal(n if d == 1 else (n * np.uint64(_fastdiv_m(d))) >> np.uint64(32), n // np.uint64(d))
+
+
+def test_fastdiv_units_guard_keeps_every_division_exact():
+    """FastDiv::div(n) = (n * ceil(2^32 / d)) >> 32 is n / d only while n * (ceil(2^32 / d) * d - 2^32) < 2^32.
+    apg_image_step's re-choice of the units per workgroup can make 1 into 2 for any sensor size; unguarded, a
+    255 x 255 sensor then divides q = 130049 by 65025 into unit 2 of a two-unit workgroup.  fastdiv_safe_units lowers
+    the units until the divisions by per, s1 and s0 + s1 are exact, for every sensor up to 256 x 256 (the kernels'
+    limit, GS_MAX_SIDE; the host refuses glimpses of more than 16384 values today, below the affected sizes)."""
+    resident = 1024
+    n = np.arange(1, 4 * resident + 1, dtype=np.int64)
+    # unguarded: the wrong quotient, and the smallest affected sensor
+    per = 255 * 255
+    assert 2 in _fused_units(min(64, _units_per_block(per, 8)), n, resident)
+    assert 130049 // per == 1 and _fastdiv_div(130049, per) == 2
+    assert not _fastdiv_exact(per, 2 * per - 1)
+    products = sorted({s0 * s1 for s0 in range(1, 257) for s1 in range(s0, 257)})
+    affected = [p for p in products if not _fastdiv_exact(p, 2 * p - 1)]
+    assert affected[0] == 46805 == 185 * 253 and not _fastdiv_all_exact(46805, 2 * 46805 - 1)
+    assert all(_fastdiv_all_exact(p, 2 * p - 1) for p in products if 46000 <= p < 46805)
+    assert all(p & (p - 1) for p in affected) and _fastdiv_exact(65536, 2 * 65536 - 1)  # powers of two: exact
+    assert _safe_units(2, 185, 253) == 1 and _safe_units(2, 255, 255) == 1 and _safe_units(2, 256, 256) == 2
+    # guarded: every units-per-workgroup value either launcher can reach, for every sensor
+    fused = {u0: set(np.unique(_fused_units(u0, n, resident)).tolist()) for u0 in range(1, 65)}
+    lowered = 0
+    for s0 in range(1, 257):
+        for s1 in range(s0, 257):
+            per, side = s0 * s1, s0 + s1
+            cand = fused[min(64, _units_per_block(per, 8))] | {_units_per_block(per, ppt) for ppt in range(1, 17)}
+            for upb in cand:
+                safe = _safe_units(upb, s0, s1)
+                lowered += safe != upb
+                assert 1 <= safe <= upb
+                # the largest q each division sees: q < units * per by per, pix < per by s1, q < units * side by side
+                assert _fastdiv_exact(per, safe * per - 1) and _fastdiv_exact(side, safe * side - 1), (s0, s1, upb)
+                assert _fastdiv_exact(s1, per - 1) and _fastdiv_exact(s0, per - 1)  # (the sensor either way round)
+                assert _safe_units(upb, s1, s0) == safe
+    assert lowered > 0
+    # the condition against the division itself, every q, where the guard acts and at the edges around it
+    for s0, s1 in ((185, 253), (255, 255), (256, 256), (181, 256), (1, 1), (1, 256), (5, 5), (3, 7)):
+        per = s0 * s1
+        for upb in fused[min(64, _units_per_block(per, 8))]:
+            safe = _safe_units(upb, s0, s1)
+            assert _fastdiv_all_exact(per, safe * per - 1) and _fastdiv_all_exact(s1, per - 1)
+            assert _fastdiv_all_exact(s0 + s1, safe * (s0 + s1) - 1)

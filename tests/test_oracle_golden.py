@@ -187,7 +187,8 @@ def test_vector_env_trace(oracle_mod, name):
 
 
 IMAGE_CASES = ["cls_mnist", "cls_tin", "cls_gray3_rect", "loc_mnist", "loc_tin12", "loc_rect",
-               "cls_mnist_sparse", "loc_rect_sparse"]  # *_sparse: SparsifyVectorWrapper over the log wrapper
+               "cls_mnist_sparse", "loc_rect_sparse",  # *_sparse: SparsifyVectorWrapper over the log wrapper
+               "cls_f32rgb", "loc_f64gray3"]  # float pools in [-0.2, 1.2]: cast to float32, not divided by 255
 
 
 @pytest.mark.parametrize("name", IMAGE_CASES)
