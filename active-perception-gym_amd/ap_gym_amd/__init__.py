@@ -18,6 +18,7 @@ from .circle_square import (  # noqa: F401
 )
 from .floor_map import (ArrayFloorMapDataset, FloorMapDataset, FloorMapDatasetMaze, FloorMapDatasetRooms,  # noqa: F401
                         ForeignFloorMapView, PoolFloorMapDataset)
+from .glimpse_poses import ImageMoveResult, image_glimpse_scores, image_glimpses_at, image_move_positions  # noqa: F401
 from .image_dataset import (  # noqa: F401
     ArrayImageClassificationDataset,
     HuggingfaceImageClassificationDataset,

@@ -31,6 +31,7 @@ APG_ERR_OOB_X = 16
 APG_ERR_PREFETCH = 32
 APG_ERR_NO_FREE_CELL = 64
 APG_ERR_INDEX = 128  # unpack_maps / scan_poses / move_poses: a map id outside [0, n_src) (raised as IndexError)
+#                      image_glimpse_scores: a pool index outside [0, pool_len)
 APG_ERR_BAD_POSE = 256  # scan_poses / move_poses: a pose or candidate action with a non-finite coordinate (ValueError)
 #                         pf_resample: a particle with such a pose, or with a NaN or +inf log-weight
 #                         scan_spread: a hypothesis with such a pose, or with a weight that is NaN or outside [0, 1]
@@ -62,6 +63,13 @@ SCAN_SPREAD_TILE = 256
 SCAN_SPREAD_MAX_K = 4096
 SCAN_SPREAD_MAX_BEAMS = 1024
 SCAN_SPREAD_MAX_GRID = 8192
+# k_glimpse_scores / k_image_move (csrc/apg_glimpse_poses.hip GP_MAX_SCORE_L, GP_MAX_T; apg_glimpse.hpp GS_MAX_SIDE;
+# apg_pairwise.hpp MAX_PW_N): values per glimpse the fused score takes (its glimpses and the observed block live in
+# LDS), sensor side and values per glimpse of the glimpse output, actions per candidate
+GLIMPSE_SCORES_MAX_L = 4096
+GLIMPSE_MAX_SIDE = 256
+GLIMPSE_MAX_L = 16384
+IMAGE_MOVE_MAX_T = 4096
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -255,6 +263,10 @@ SYMBOLS = [
     ("apg_image_discard_ahead", ctypes.c_int, [ctypes.POINTER(ImageConfig), ctypes.POINTER(ImageState), _vp]),
     ("apg_image_glimpse", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, _vp, ctypes.c_int, ctypes.c_int32,
                                          _vp, _vp, _vp]),
+    ("apg_image_glimpse_scores", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, _vp, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("apg_image_move", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, ctypes.c_int64, ctypes.c_int32,
+                                      ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     ("apg_image_unique_top_k", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, _vp, ctypes.c_int32,
                                               ctypes.c_int32, _vp, _vp, _vp]),
     ("apg_loss_ce", ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _vp,

@@ -450,6 +450,8 @@ class _ImageVectorEnv(VectorEnv):
             raise ValueError(OOB_MSG % 0)
         if bits & N.APG_ERR_OOB_X:
             raise ValueError(OOB_MSG % 1)
+        if bits & N.APG_ERR_INDEX:
+            raise IndexError("env id outside [0, num_envs) in glimpses_at / glimpse_scores / lookahead")
 
     def check_errors(self, block: bool = True):
         if block:
@@ -823,6 +825,176 @@ class _ImageVectorEnv(VectorEnv):
         if self.log_stats and terminated:
             info["stats"] = self._torch_stats()
         return self._torch_obs(), self._c(T["reward"]), term, trunc, info
+
+    # ------------------------------------------------------------------ glimpses at chosen positions
+    def _env_ids_tensor(self, env_ids):
+        """`env_ids` (any integer tensor on any device, a numpy array, a list, one int; None stays None) as a
+        contiguous 1-d int64 tensor on the env's device."""
+        import torch
+
+        if env_ids is None:
+            return None
+        if isinstance(env_ids, torch.Tensor):
+            if env_ids.is_floating_point() or env_ids.is_complex() or env_ids.dtype == torch.bool:
+                raise TypeError(f"env_ids must hold integers, got {env_ids.dtype}")
+            return env_ids.to(device=self._dev, dtype=torch.int64).reshape(-1).contiguous()
+        ids = np.asarray(env_ids)
+        if ids.size and ids.dtype.kind not in "iu":
+            raise TypeError(f"env_ids must hold integers, got {ids.dtype}")
+        return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64).reshape(-1), device=self._dev)
+
+    def _chosen(self, env_ids):
+        """(ids or None, M, a row selector for per-env state, the pool index of each chosen sub-env).  An id outside
+        [0, num_envs) reads sub-env 0's rows, gets pool index -1 (never read: NaN glimpses) and sets APG_ERR_INDEX."""
+        import torch
+
+        if self._closed:
+            raise RuntimeError("environment is closed")
+        ids = self._env_ids_tensor(env_ids)
+        if ids is None:
+            return None, self.num_envs, (lambda x: x), self._t["index"]
+        valid = (ids >= 0) & (ids < self.num_envs)
+        safe = torch.where(valid, ids, torch.zeros_like(ids))
+        if ids.numel():
+            self._t["err"].bitwise_or_((~valid).any().to(torch.int32) * N.APG_ERR_INDEX)
+        index = torch.where(valid, self._t["index"][safe], torch.full_like(ids, -1))
+        return ids, ids.shape[0], (lambda x: x[safe]), index
+
+    def _positions(self, positions, m):
+        """`positions` as a contiguous float64 / float32 [M, K, 2] device tensor, and whether K was given."""
+        import torch
+
+        p = torch.as_tensor(positions, device=self._dev)
+        if p.dtype not in (torch.float64, torch.float32):
+            p = p.to(torch.float64)
+        has_k = p.dim() == 3
+        if p.dim() == 2:
+            p = p[:, None, :]
+        if p.dim() != 3 or p.shape[2] != 2 or p.shape[0] != m:
+            raise ValueError(f"positions must have shape [{m}, K, 2] or [{m}, 2] (one set per chosen sub-env), got "
+                             f"{tuple(torch.as_tensor(positions).shape)}")
+        return p.contiguous(), has_k
+
+    def _glimpse_geometry(self):
+        c = self._cfg
+        return dict(image_size=self.image_size, sensor_size=(c.sensor_h, c.sensor_w), sensor_scale=c.sensor_scale,
+                    channels=c.channels, tiled=c.pool_dtype == N.APG_POOL_U8_TILED)
+
+    def _pose_result(self, res, out):
+        """numpy backend: the device result as a numpy array (`out`, when given, filled and returned), errors raised
+        at once.  torch backend: the tensor itself (errors are raised lazily by check_errors())."""
+        if self.array_backend != "numpy":
+            return res
+        host = res.cpu().numpy()
+        self.check_errors(block=True)
+        if out is None:
+            return host
+        np.copyto(out, host.reshape(out.shape), casting="no")
+        return out
+
+    def glimpses_at(self, positions=None, env_ids=None, *, out=None):
+        """What the sensor would see at `positions` [M, K, 2] (normalised (x, y) as obs["glimpse_pos"], float64 or
+        float32, K positions per chosen sub-env; [M, 2] for one each) on the current images of the sub-envs `env_ids`
+        (any order, duplicates allowed; None: every sub-env): float32 [M, K, s0, s1, C] ([M, s0, s1, C] for [M, 2]),
+        the env's exact glimpse (glimpse_poses.image_glimpses_at on the env's pool).  positions=None takes the
+        sub-envs' own float64 positions and equals obs["glimpse"] bit for bit; the float32 targets of a localization
+        env give obs["target_glimpse"].  Nothing in the env changes.  A position whose glimpse leaves the image (or
+        that is not finite) yields NaN and raises the reference's ValueError, an env id outside [0, num_envs) yields
+        NaN and raises IndexError, both through check_errors() (torch backend: lazily; numpy backend: at once).  The
+        numpy backend takes and returns numpy arrays; the torch backend returns device tensors (`out`: a contiguous
+        device tensor to write into)."""
+        from .glimpse_poses import image_glimpses_at
+
+        _, m, rows, index = self._chosen(env_ids)
+        p, has_k = self._positions(rows(self._t["pos"]) if positions is None else positions, m)
+        torch_out = out if self.array_backend != "numpy" else None
+        if torch_out is not None and not has_k:
+            torch_out = torch_out.unsqueeze(1)
+        res = image_glimpses_at(self._t["pool"], index.contiguous(), p, out=torch_out, err=self._t["err"],
+                                **self._glimpse_geometry())
+        return self._pose_result(res if has_k else res[:, 0], out)
+
+    def glimpse_scores(self, positions, observed=None, env_ids=None, *, out=None):
+        """Mean squared difference [M, K] ([M] for positions [M, 2]) between the glimpse at each of `positions` and
+        `observed` [M, s0, s1, C] (None: the chosen sub-envs' current obs["target_glimpse"] for a localization env,
+        their current obs["glimpse"] otherwise), np.mean((g - observed) ** 2, axis=(-3, -2, -1)) in float32 as numpy
+        evaluates it (glimpse_poses.image_glimpse_scores): 0.0 exactly for a position that reproduces the
+        observation.  The glimpses are not written to memory.  Arguments and errors as glimpses_at()."""
+        import torch
+
+        from .glimpse_poses import image_glimpse_scores
+
+        _, m, rows, index = self._chosen(env_ids)
+        p, has_k = self._positions(positions, m)
+        if observed is None:
+            observed = rows(self._t["target_glimpse" if self.kind == N.APG_IMAGE_LOCALIZE else "glimpse"])
+        observed = torch.as_tensor(observed, dtype=torch.float32, device=self._dev).contiguous()
+        torch_out = out if self.array_backend != "numpy" else None
+        if torch_out is not None and not has_k:
+            torch_out = torch_out.unsqueeze(1)
+        res = image_glimpse_scores(self._t["pool"], index.contiguous(), p, observed, out=torch_out,
+                                   err=self._t["err"], **self._glimpse_geometry())
+        return self._pose_result(res if has_k else res[:, 0], out)
+
+    def lookahead(self, actions, env_ids=None, *, glimpses="last"):
+        """Where would these actions take the sensor, and what would it see?  `actions` [M, K, T, 2] (or [M, K, 2] for
+        T = 1): K candidate sequences of T actions for each of the sub-envs `env_ids` (any order, duplicates allowed;
+        None: every sub-env), rolled out open-loop from the sub-env's current position on its current image with the
+        env's own move (glimpse_poses.image_move_positions), bit for bit what step() does -- and without touching the
+        env: no position, index, RNG stream, draw-ahead buffer, output buffer or step count changes.  Returns a dict:
+
+          pos            float64 [M, K, T, 2] the position after each action; after the last applied action it repeats
+          glimpse_pos    float32 [M, K, T, 2] obs["glimpse_pos"] after each action
+          base_reward    float32 [M, K, T] info["base_reward"] of each action, 0 for actions that are not applied
+          steps          int32 [M, K] the actions applied: min(T, step limit - steps taken in the episode)
+          terminated     bool [M, K]: the episode's step limit is reached within these actions
+          glimpse        obs["glimpse"] at the positions: glimpses="last" [M, K, s0, s1, C] at pos[:, :, -1];
+                         glimpses="all" [M, K, T, s0, s1, C]; glimpses=None: absent
+          pending_reset  bool [M]: the batch's episode is over and its next step() autoresets.  The rollout then starts
+                         from the finished episode's position on its old image (what the env still holds) with no
+                         step limit (steps = T, terminated False); step() will not continue from there.
+
+        A NaN action gives NaN from that action on and raises ValueError, an env id outside [0, num_envs) IndexError,
+        both through check_errors() (torch backend: lazily; numpy backend: at once).  The numpy backend takes and
+        returns numpy arrays; the torch backend returns device tensors."""
+        import torch
+
+        from .glimpse_poses import image_glimpses_at, image_move_positions
+
+        if glimpses not in ("last", "all", None):
+            raise ValueError(f"glimpses must be 'last', 'all' or None, got {glimpses!r}")
+        a = torch.as_tensor(actions, dtype=torch.float32, device=self._dev)
+        if a.dim() == 3:
+            a = a.unsqueeze(2)
+        if a.dim() != 4 or a.shape[3] != 2:
+            raise ValueError(f"actions must have shape [M, K, T, 2] or [M, K, 2], got {tuple(a.shape)}")
+        a = a.contiguous()
+        m, k, t = a.shape[0], a.shape[1], a.shape[2]
+        _, want, rows, index = self._chosen(env_ids)
+        if m != want:
+            raise ValueError(f"actions must have one candidate set per chosen sub-env ({want}), got {m}")
+        pending = bool(self._prev_done)
+        left = t if pending else int(self.config.step_limit) - int(self._t_step)
+        steps = min(t, left)
+        err = self._t["err"]
+        c = self._cfg
+        res = image_move_positions(rows(self._t["pos"]).contiguous(), a, max_step_length=(c.max_step[0], c.max_step[1]),
+                                   max_steps=steps, err=err)
+        dev = self._dev
+        out = dict(pos=res.pos, glimpse_pos=res.glimpse_pos, base_reward=res.base_reward,
+                   steps=torch.full((m, k), steps, dtype=torch.int32, device=dev),
+                   terminated=torch.full((m, k), (not pending) and steps >= left, dtype=torch.bool, device=dev))
+        if glimpses is not None:
+            at = res.pos if glimpses == "all" else res.pos[:, :, -1:, :]
+            g = image_glimpses_at(self._t["pool"], index.contiguous(), at.reshape(m, k * at.shape[2], 2).contiguous(),
+                                  err=err, **self._glimpse_geometry())
+            out["glimpse"] = g.view((m, k, t) + tuple(g.shape[2:]) if glimpses == "all" else (m, k) + tuple(g.shape[2:]))
+        out["pending_reset"] = torch.full((m,), pending, dtype=torch.bool, device=dev)
+        if self.array_backend != "numpy":
+            return out
+        out = {name: v.cpu().numpy() for name, v in out.items()}
+        self.check_errors(block=True)
+        return out
 
     # ------------------------------------------------------------------ render
     def _track_render(self, prediction, resetting: bool):

@@ -20,6 +20,10 @@
 //   torch.ops.apgym.lidar_pf_resample(Tensor poses, Tensor? logw, Tensor? score, Tensor? u, float score_scale,
 //                                     float ess_frac, Tensor? weight, Tensor? estimate, Tensor? ess, Tensor? index,
 //                                     Tensor? poses_out, Tensor? logw_out, Tensor? resampled, Tensor? err) -> ()
+//   torch.ops.apgym.image_glimpse_scores(Tensor pool, int[] geo, float sensor_scale, Tensor index, Tensor positions,
+//                                        Tensor? observed, Tensor? score, Tensor? glimpse, Tensor? err) -> ()
+//   torch.ops.apgym.image_move(Tensor start, Tensor actions, float msl0, float msl1, int max_steps, Tensor pos,
+//                              Tensor glimpse_pos, Tensor base_reward, Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -489,6 +493,119 @@ void lidar_scan_spread(const at::Tensor &bits, int64_t width, const at::Tensor &
   check(apg_lidar_scan_spread(&a, stream_of(dev)), "apg_lidar_scan_spread");
 }
 
+// Glimpses and fused match scores of the image envs at caller-chosen positions (apg_image_glimpse_scores).  pool: the
+// image pool as the envs hold it (uint8 with APG_U8_POOL_PAD readable bytes behind it, row-major or RGBX tiles, or
+// float32); geo: height, width, pool_channels, channels, pool_dtype, sensor_h, sensor_w, pool_len; index: int64 [M];
+// positions: float64 or float32 [M, K, 2]; observed: float32 [M, s0, s1, C] or None (needed with score); score:
+// float32 [M, K] or None; glimpse: float32 [M, K, s0, s1, C] or None; err: int32 [1] or None.
+void image_glimpse_scores(const at::Tensor &pool, std::vector<int64_t> geo, double sensor_scale, const at::Tensor &index,
+                          const at::Tensor &positions, const c10::optional<at::Tensor> &observed,
+                          const c10::optional<at::Tensor> &score, const c10::optional<at::Tensor> &glimpse,
+                          const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(pool.is_cuda(), "pool must be on a GPU device, got ", pool.device());
+  const at::Device dev = pool.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(geo.size() == 8, "geo: height, width, pool_channels, channels, pool_dtype, sensor_h, sensor_w, pool_len");
+  for (int i = 0; i < 7; i++) TORCH_CHECK(geo[i] >= 0 && geo[i] <= INT32_MAX, "geo[", i, "] out of range");
+  apg_image_config c{};
+  c.num_envs = c.num_envs_total = 1;
+  c.kind = APG_IMAGE_LOCALIZE;
+  c.step_limit = 1;
+  c.height = (int32_t)geo[0];
+  c.width = (int32_t)geo[1];
+  c.pool_channels = (int32_t)geo[2];
+  c.channels = (int32_t)geo[3];
+  c.pool_dtype = (int32_t)geo[4];
+  c.sensor_h = (int32_t)geo[5];
+  c.sensor_w = (int32_t)geo[6];
+  c.pool_len = geo[7];
+  c.sensor_scale = sensor_scale;
+  TORCH_CHECK(pool.is_contiguous(), "pool must be contiguous");
+  TORCH_CHECK(pool.scalar_type() == (c.pool_dtype == APG_POOL_F32 ? at::kFloat : at::kByte),
+              "pool must be ", c.pool_dtype == APG_POOL_F32 ? "float32" : "uint8", " for this pool_dtype");
+  const int64_t img = c.pool_dtype == APG_POOL_U8_TILED
+                          ? ((geo[0] + 3) / 4) * ((geo[1] + 7) / 8) * 128
+                          : geo[0] * geo[1] * geo[2];
+  TORCH_CHECK(c.pool_len >= 1 && pool.numel() == c.pool_len * img, "pool must hold pool_len images of ", img,
+              " elements, got ", pool.numel());
+  if (c.pool_dtype != APG_POOL_F32)
+    TORCH_CHECK((int64_t)pool.storage().nbytes() - pool.storage_offset() >= pool.numel() + APG_U8_POOL_PAD,
+                "a uint8 pool needs APG_U8_POOL_PAD readable bytes behind it in its allocation");
+  TORCH_CHECK(positions.dim() == 3 && positions.size(2) == 2, "positions must be [M, K, 2]");
+  const int64_t m = positions.size(0), k = positions.size(1);
+  TORCH_CHECK(k <= INT32_MAX, "positions: too many positions per set");
+  TORCH_CHECK(positions.device() == dev && positions.is_contiguous() &&
+                  (positions.scalar_type() == at::kDouble || positions.scalar_type() == at::kFloat),
+              "positions must be a contiguous float64 or float32 tensor on ", dev);
+  TORCH_CHECK(index.device() == dev && index.scalar_type() == at::kLong && index.dim() == 1 && index.is_contiguous() &&
+                  index.numel() == m,
+              "index must be a contiguous int64 [M] tensor on ", dev);
+  const int64_t l = geo[5] * geo[6] * geo[3];
+  const float *obs = nullptr;
+  float *sc = nullptr, *gl = nullptr;
+  uint32_t *errp = nullptr;
+  if (observed.has_value() && observed->defined()) {
+    check_io(*observed, dev, m * l, "observed");
+    obs = reinterpret_cast<const float *>(ptr(*observed));
+  }
+  if (score.has_value() && score->defined()) {
+    check_io(*score, dev, m * k, "score");
+    TORCH_CHECK(obs || m * l == 0, "score needs observed");
+    sc = reinterpret_cast<float *>(ptr(*score));
+  }
+  if (glimpse.has_value() && glimpse->defined()) {
+    check_io(*glimpse, dev, m * k * l, "glimpse");
+    gl = reinterpret_cast<float *>(ptr(*glimpse));
+  }
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    errp = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  if (m * k == 0 || (!sc && !gl)) return;
+  check(apg_image_glimpse_scores(&c, ptr(pool), reinterpret_cast<const int64_t *>(ptr(index)), ptr(positions),
+                                 positions.scalar_type() == at::kFloat ? 1 : 0, m, (int32_t)k, obs, sc, gl, errp,
+                                 stream_of(dev)),
+        "apg_image_glimpse_scores");
+}
+
+// Open-loop rollouts of candidate actions with the image envs' move (apg_image_move).  start: float64 [M, 2];
+// actions: float32 [M, K, T, 2]; pos: float64 [M, K, T, 2]; glimpse_pos: float32 [M, K, T, 2]; base_reward: float32
+// [M, K, T]; err: int32 [1] or None.
+void image_move(const at::Tensor &start, const at::Tensor &actions, double msl0, double msl1, int64_t max_steps,
+                at::Tensor pos, at::Tensor glimpse_pos, at::Tensor base_reward, const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(start.is_cuda(), "start must be on a GPU device, got ", start.device());
+  const at::Device dev = start.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(actions.dim() == 4 && actions.size(3) == 2, "actions must be [M, K, T, 2]");
+  const int64_t m = actions.size(0), k = actions.size(1), t = actions.size(2);
+  TORCH_CHECK(k <= INT32_MAX && t >= 1 && t <= 4096, "actions: T must be in [1, 4096]");
+  TORCH_CHECK(max_steps >= 0, "max_steps must be >= 0");
+  TORCH_CHECK(start.scalar_type() == at::kDouble && start.is_contiguous() && start.numel() == 2 * m,
+              "start must be a contiguous float64 [M, 2] tensor");
+  check_io(actions, dev, 2 * m * k * t, "actions");
+  TORCH_CHECK(pos.device() == dev && pos.scalar_type() == at::kDouble && pos.is_contiguous() &&
+                  pos.numel() == 2 * m * k * t,
+              "pos must be a contiguous float64 [M, K, T, 2] tensor on ", dev);
+  check_io(glimpse_pos, dev, 2 * m * k * t, "glimpse_pos");
+  check_io(base_reward, dev, m * k * t, "base_reward");
+  uint32_t *errp = nullptr;
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    errp = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  if (m * k == 0) return;
+  apg_image_config c{};
+  c.max_step[0] = msl0;
+  c.max_step[1] = msl1;
+  check(apg_image_move(&c, reinterpret_cast<const double *>(ptr(start)), reinterpret_cast<const float *>(ptr(actions)),
+                       m, (int32_t)k, (int32_t)t, (int32_t)std::min<int64_t>(max_steps, INT32_MAX),
+                       reinterpret_cast<double *>(ptr(pos)), reinterpret_cast<float *>(ptr(glimpse_pos)),
+                       reinterpret_cast<float *>(ptr(base_reward)), errp, stream_of(dev)),
+        "apg_image_move");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -519,4 +636,10 @@ TORCH_LIBRARY(apgym, m) {
   m.def("lidar_scan_spread(Tensor bits, int width, Tensor poses, Tensor? weight, Tensor? map_ids, Tensor beam_dirs, "
         "float lidar_range, Tensor(a!)? spread, Tensor(b!)? mean, Tensor(c!)? err) -> ()",
         lidar_scan_spread);
+  m.def("image_glimpse_scores(Tensor pool, int[] geo, float sensor_scale, Tensor index, Tensor positions, "
+        "Tensor? observed, Tensor(a!)? score, Tensor(b!)? glimpse, Tensor(c!)? err) -> ()",
+        image_glimpse_scores);
+  m.def("image_move(Tensor start, Tensor actions, float msl0, float msl1, int max_steps, Tensor(a!) pos, "
+        "Tensor(b!) glimpse_pos, Tensor(c!) base_reward, Tensor(d!)? err) -> ()",
+        image_move);
 }

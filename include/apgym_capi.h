@@ -48,6 +48,9 @@
  *   apg_image_glimpse
  *       ImagePerceptionModule.get_glimpse  image_perception_module.py:294-331 (scipy
  *       RegularGridInterpolator "linear", bounds_error=True; clip(0, 1); float32).
+ *   apg_image_glimpse_scores / apg_image_move
+ *       the same glimpse at caller-chosen positions with a fused match score (image_perception_module.py:268-270's
+ *       np.mean((a - b) ** 2)), and the module's move (:197-213) for candidate actions.
  *   apg_image_unique_top_k
  *       ImagePerceptionModule.sample_unique_glimpse_positions  image_perception_module.py:253-277.
  *   apg_loss_ce / apg_loss_mse
@@ -87,7 +90,8 @@ extern "C" {
 #define APG_ERR_NO_FREE_CELL 64u  /* a pool map without a free cell was drawn: numpy's integers(0, 0) raises
                                      ValueError("high <= 0") in reset (lidar_localization2d.py:302-303) */
 #define APG_ERR_INDEX 128u        /* apg_lidar_unpack_maps / apg_lidar_scan_poses / apg_lidar_move_poses: a map id
-                                     outside [0, n_src) (raised as IndexError) */
+                                     outside [0, n_src); apg_image_glimpse_scores: a pool index outside [0, pool_len)
+                                     (raised as IndexError) */
 #define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses / apg_lidar_move_poses: a pose (or a candidate action) with a
                                      non-finite coordinate; apg_lidar_pf_resample: a particle with such a pose or with a
                                      NaN or +inf log-weight (raised as ValueError) */
@@ -625,6 +629,34 @@ int apg_image_discard_ahead(const apg_image_config *cfg, const apg_image_state *
  * [N][npos][sensor_h][sensor_w][C]; index[N] selects the pool image of each env (u8 pools: + APG_U8_POOL_PAD). */
 int apg_image_glimpse(const apg_image_config *cfg, const void *pool, const int64_t *index, const void *pos,
                       int pos_is_f32, int32_t npos, float *out, uint32_t *err, apg_stream_t stream);
+
+/* Glimpses and fused match scores at caller-chosen positions (an addition to ABI 0.4; no struct changes).  For each
+ * position set i of m: k candidate positions pos[i][j] (f64 or f32, pos_is_f32; normalised (x, y) as
+ * obs["glimpse_pos"]) on pool image index[i].  The geometry (image and sensor size, sensor_scale, channels, pool format,
+ * pool_len) comes from cfg, as for apg_image_glimpse; cfg->num_envs is not used.
+ *   glimpse [m][k][sensor_h][sensor_w][C] (may be NULL): the env's glimpse at each position -- with a sub-env's f64
+ *           position obs["glimpse"], with its f32 target obs["target_glimpse"], bit for bit.
+ *   score   [m][k] (may be NULL; needs observed [m][sensor_h][sensor_w][C]): np.mean((g - observed[i]) ** 2,
+ *           axis=(-3, -2, -1)) in float32 as numpy evaluates it on a contiguous block (pairwise sum of the
+ *           L = sensor_h * sensor_w * C squares, (0 + sum) / L): exactly 0.0 where the candidate reproduces observed[i],
+ *           NaN where observed[i] holds a NaN.  The glimpses are not written to memory unless glimpse is given.
+ * Limits: sensor sides <= 256, m * k * sensor_h * sensor_w < 2^31, L <= 16384; with score, L <= 4096 (the glimpses of
+ * a workgroup and observed[i] live in LDS): APG_E_INVALID beyond.  A position whose sampling coordinates leave the
+ * image (the reference's bounds_error=True) or that is not finite yields NaN (score and glimpse) and ORs APG_ERR_OOB_X /
+ * APG_ERR_OOB_Y into *err; an index outside [0, pool_len) is never read, yields NaN and sets APG_ERR_INDEX (err may
+ * be NULL).  Other units are unaffected.  m == 0 or k == 0 launches nothing. */
+int apg_image_glimpse_scores(const apg_image_config *cfg, const void *pool, const int64_t *index, const void *pos,
+                             int pos_is_f32, int64_t m, int32_t k, const float *observed, float *score, float *glimpse,
+                             uint32_t *err, apg_stream_t stream);
+
+/* Open-loop rollouts of candidate actions with the image envs' move (ImagePerceptionModule.step: project_sphere in
+ * f32, cfg->max_step in f64, clip to [-1, 1]; an addition to ABI 0.4).  start [m][2] (f64), actions [m][k][t][2]
+ * (1 <= t <= 4096) -> pos [m][k][t][2] (f64), glimpse_pos [m][k][t][2] (the observation's f32 value), base_reward
+ * [m][k][t] = -|action| * 1e-3 (f32).  After max_steps (>= 0) actions the pose repeats and the base reward is 0.  A
+ * NaN action gives NaN from that action on and ORs APG_ERR_NAN_ACTION into *err (may be NULL). */
+int apg_image_move(const apg_image_config *cfg, const double *start, const float *actions, int64_t m, int32_t k,
+                   int32_t t, int32_t max_steps, double *pos, float *glimpse_pos, float *base_reward, uint32_t *err,
+                   apg_stream_t stream);
 
 /* Uniqueness ranking of sample_unique_glimpse_positions: top_k[N][k] grid indices by descending
  * min_{b != a} mean((g_b - g_a)^2) (exact ties: ascending index); uniq[N][P] (float, may be NULL). */
