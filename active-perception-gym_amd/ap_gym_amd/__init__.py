@@ -39,11 +39,13 @@ from .loss_fn import (  # noqa: F401
 )
 from .map_bits import unpack_map_bits  # noqa: F401
 from .move_poses import MovePosesResult, lidar_move_poses  # noqa: F401
+from .overlap_scores import OverlapScoresResult, image_overlap_scores  # noqa: F401
 from .particle_filter import LidarParticleFilter  # noqa: F401
 from .pf_resample import PfResampleResult, lidar_pf_resample  # noqa: F401
 from .scan_poses import lidar_pose_scores, lidar_scan_poses  # noqa: F401
 from .scan_spread import ScanSpreadResult, lidar_scan_spread  # noqa: F401
 from .registration import make_vec, register, registry  # noqa: F401
+from .target_belief import ImageTargetBelief, TargetBeliefResult  # noqa: F401
 from .spaces import ActivePerceptionActionSpace, ImageSpace, LogitSpace  # noqa: F401
 
 __version__ = "0.1.0"

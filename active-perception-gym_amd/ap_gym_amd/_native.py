@@ -35,6 +35,7 @@ APG_ERR_INDEX = 128  # unpack_maps / scan_poses / move_poses: a map id outside [
 APG_ERR_BAD_POSE = 256  # scan_poses / move_poses: a pose or candidate action with a non-finite coordinate (ValueError)
 #                         pf_resample: a particle with such a pose, or with a NaN or +inf log-weight
 #                         scan_spread: a hypothesis with such a pose, or with a weight that is NaN or outside [0, 1]
+#                         image_overlap_scores: a glimpse position or a hypothesis with a non-finite coordinate
 # k_scan_poses' work split (csrc/apg_scan_poses.hip SP_TILE, SP_MAX_MPW, SP_MAX_GRID): rays per workgroup pass, pose
 # sets a workgroup takes at once when a set is small, workgroups per launch
 SCAN_POSES_TILE = 256
@@ -70,6 +71,13 @@ GLIMPSE_SCORES_MAX_L = 4096
 GLIMPSE_MAX_SIDE = 256
 GLIMPSE_MAX_L = 16384
 IMAGE_MOVE_MAX_T = 4096
+# k_overlap_scores (csrc/apg_overlap_scores.hip OV_MAX_L, OV_MAX_CHUNK, OV_MIN_CHUNK, OV_FILL_WGS): values per glimpse
+# (both glimpses of a set live in LDS), hypotheses per workgroup: the largest, the smallest, and the launch size under
+# which the chunk is halved (overlap_scores_chunk restates the choice; apg_image_overlap_chunk is the library's)
+OVERLAP_SCORES_MAX_L = 4096
+OVERLAP_SCORES_MAX_CHUNK = 64
+OVERLAP_SCORES_MIN_CHUNK = 8
+OVERLAP_SCORES_FILL_WGS = 1024
 APG_UNPACK_F32 = 0
 APG_UNPACK_F16 = 1
 APG_UNPACK_BF16 = 2
@@ -158,6 +166,15 @@ class ScanSpreadArgs(ctypes.Structure):
         ("n_src", ctypes.c_int64), ("m", ctypes.c_int64)] + [
         (n, ctypes.c_int32) for n in ("height", "width", "a", "k", "beams")] + [
         ("lidar_range", ctypes.c_float)]
+
+
+class OverlapScoresArgs(ctypes.Structure):
+    _fields_ = [(n, _vp) for n in ("glimpse", "target_glimpse", "glimpse_pos", "hypotheses", "logw", "sse", "count",
+                                   "logw_out", "err")] + [
+        ("m", ctypes.c_int64)] + [
+        (n, ctypes.c_int32) for n in ("k", "height", "width", "sensor_h", "sensor_w", "channels", "pos_is_f32",
+                                      "hyp_is_f32", "hyp_shared")] + [
+        ("gain", ctypes.c_float), ("tau", ctypes.c_float), ("sensor_scale", ctypes.c_double)]
 
 
 class LidarSizes(ctypes.Structure):
@@ -267,6 +284,8 @@ SYMBOLS = [
                                                 ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     ("apg_image_move", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("apg_image_overlap_scores", ctypes.c_int, [ctypes.POINTER(OverlapScoresArgs), _vp]),
+    ("apg_image_overlap_chunk", ctypes.c_int32, [ctypes.c_int64, ctypes.c_int32]),
     ("apg_image_unique_top_k", ctypes.c_int, [ctypes.POINTER(ImageConfig), _vp, _vp, _vp, ctypes.c_int32,
                                               ctypes.c_int32, _vp, _vp, _vp]),
     ("apg_loss_ce", ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _vp,
@@ -356,6 +375,16 @@ def torch_ops():
             raise NativeLibraryError(f"cannot load {TORCH_LIB_PATH}: {e}") from e
         _torch_ops = torch.ops.apgym
     return _torch_ops
+
+
+def overlap_scores_chunk(m: int, k: int) -> int:
+    """Hypotheses per workgroup of k_overlap_scores for m sets of k (apg_image_overlap_chunk, restated)."""
+    if m <= 0 or k <= 0:
+        return 0
+    chunk = OVERLAP_SCORES_MAX_CHUNK
+    while chunk > OVERLAP_SCORES_MIN_CHUNK and m * ((k + chunk - 1) // chunk) < OVERLAP_SCORES_FILL_WGS:
+        chunk //= 2
+    return chunk
 
 
 def exact_device(device):

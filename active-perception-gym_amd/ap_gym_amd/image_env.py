@@ -398,6 +398,7 @@ class _ImageVectorEnv(VectorEnv):
         self._closed = False
         self._t_step = 0
         self._prev_done = False
+        self._batches = 0  # batches drawn so far: reset() and every batch autoreset step (host-side, no device read)
         self._done_consts = None
         self._stats_view = None
         # numpy backend: pinned input staging, the device byte block the step outputs are packed into and a ring of
@@ -436,6 +437,12 @@ class _ImageVectorEnv(VectorEnv):
     def current_labels(self):
         return self._t["label"]
 
+    @property
+    def batch_count(self) -> int:
+        """Batches drawn so far: one per reset() and one per batch autoreset step (the step after the one that
+        terminated every sub-env).  Known on the host; a belief over a batch's targets restarts when it changes."""
+        return self._batches
+
     def _stream(self):
         return N.stream_handle(self.device)
 
@@ -451,7 +458,10 @@ class _ImageVectorEnv(VectorEnv):
         if bits & N.APG_ERR_OOB_X:
             raise ValueError(OOB_MSG % 1)
         if bits & N.APG_ERR_INDEX:
-            raise IndexError("env id outside [0, num_envs) in glimpses_at / glimpse_scores / lookahead")
+            raise IndexError("env id outside [0, num_envs) in glimpses_at / glimpse_scores / lookahead / "
+                             "target_overlap")
+        if bits & N.APG_ERR_BAD_POSE:
+            raise ValueError("target_overlap: a hypothesis (or the glimpse position) has a non-finite coordinate")
 
     def check_errors(self, block: bool = True):
         if block:
@@ -504,6 +514,7 @@ class _ImageVectorEnv(VectorEnv):
         self._launch_draw_ahead()
         self._t_step = 0
         self._prev_done = False
+        self._batches += 1
         self._visits = [[] for _ in self.render_envs]  # module.reset clears the overlay (:184-186)
         self._last_prediction = None
         if self.array_backend == "numpy":
@@ -567,6 +578,7 @@ class _ImageVectorEnv(VectorEnv):
         if resetting:
             self._launch_draw_ahead()  # the next batch's draws, while this episode steps
             self._t_step = 0
+            self._batches += 1
             terminated = False
         else:
             self._t_step += 1
@@ -995,6 +1007,42 @@ class _ImageVectorEnv(VectorEnv):
         out = {name: v.cpu().numpy() for name, v in out.items()}
         self.check_errors(block=True)
         return out
+
+    def target_overlap(self, hypotheses, env_ids=None, *, logw=None, gain: float = 0.0, tau: float = 0.0):
+        """What do the agent's own observations say about where the target is?  `hypotheses` [M, K, 2] (or [K, 2],
+        shared by all): K hypotheses of the target position (normalised (x, y), the prediction space) for each of the
+        sub-envs `env_ids` (any order, duplicates allowed; None: every sub-env), scored on the sub-envs' current
+        obs["glimpse"], obs["glimpse_pos"] (the float32 value the agent sees) and obs["target_glimpse"] -- never on
+        the image (overlap_scores.image_overlap_scores).  Returns an OverlapScoresResult: sse float32 [M, K], count
+        int32 [M, K] and, with `logw` (float32 [M, K]), logw + gain * (tau * count - sse); `logw` itself is not
+        written.  Localization envs only.  A hypothesis with a non-finite coordinate yields NaN and raises ValueError,
+        an env id outside [0, num_envs) IndexError, both through check_errors() (torch backend: lazily; numpy
+        backend: at once).  The numpy backend takes and returns numpy arrays, the torch backend device tensors."""
+        import torch
+
+        from .overlap_scores import OverlapScoresResult, image_overlap_scores
+
+        if self.kind != N.APG_IMAGE_LOCALIZE:
+            raise TypeError("target_overlap needs a localization env: a classification env has no target glimpse")
+        _, m, rows, _ = self._chosen(env_ids)
+        h = torch.as_tensor(hypotheses, device=self._dev)
+        if h.dtype not in (torch.float64, torch.float32):
+            h = h.to(torch.float64)
+        if not ((h.dim() == 3 and h.shape[0] == m and h.shape[2] == 2) or (h.dim() == 2 and h.shape[1] == 2)):
+            raise ValueError(f"hypotheses must have shape [{m}, K, 2] (one set per chosen sub-env) or [K, 2], got "
+                             f"{tuple(h.shape)}")
+        if logw is not None:
+            logw = torch.as_tensor(logw, dtype=torch.float32, device=self._dev).contiguous()
+        c = self._cfg
+        res = image_overlap_scores(rows(self._t["glimpse"]).contiguous(), rows(self._t["glimpse_pos"]).contiguous(),
+                                   rows(self._t["target_glimpse"]).contiguous(), h.contiguous(),
+                                   image_size=self.image_size, sensor_size=(c.sensor_h, c.sensor_w),
+                                   sensor_scale=c.sensor_scale, logw=logw, gain=gain, tau=tau, err=self._t["err"])
+        if self.array_backend != "numpy":
+            return res
+        res = OverlapScoresResult(*[None if v is None else v.cpu().numpy() for v in res])
+        self.check_errors(block=True)
+        return res
 
     # ------------------------------------------------------------------ render
     def _track_render(self, prediction, resetting: bool):

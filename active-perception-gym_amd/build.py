@@ -20,7 +20,8 @@ OUT_DIR = os.path.join(HERE, "ap_gym_amd", "_lib")
 OUT = os.path.join(OUT_DIR, "libapgym_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 SOURCES = ["apg_lidar.hip", "apg_image.hip", "apg_circle_square.hip", "apg_light_dark.hip", "apg_unpack.hip",
-           "apg_scan_poses.hip", "apg_move_poses.hip", "apg_pf_resample.hip", "apg_scan_spread.hip", "apg_glimpse_poses.hip"]
+           "apg_scan_poses.hip", "apg_move_poses.hip", "apg_pf_resample.hip", "apg_scan_spread.hip", "apg_glimpse_poses.hip",
+           "apg_overlap_scores.hip"]
 HEADERS = ["apg_device.hpp", "apg_maps.hpp", "apg_scan.hpp", "apg_rng.hpp", "apg_host.hpp", "apg_pairwise.hpp",
            "apg_ziggurat.hpp", "apg_maze.hpp", "apg_binom_table.hpp", "apg_rows_lds.hpp", "apg_glimpse.hpp"]
 

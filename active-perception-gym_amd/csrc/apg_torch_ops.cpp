@@ -24,6 +24,9 @@
 //                                        Tensor? observed, Tensor? score, Tensor? glimpse, Tensor? err) -> ()
 //   torch.ops.apgym.image_move(Tensor start, Tensor actions, float msl0, float msl1, int max_steps, Tensor pos,
 //                              Tensor glimpse_pos, Tensor base_reward, Tensor? err) -> ()
+//   torch.ops.apgym.image_overlap_scores(Tensor glimpse, Tensor glimpse_pos, Tensor target_glimpse, Tensor hypotheses,
+//                                        int[] image_size, float sensor_scale, Tensor? logw, float gain, float tau,
+//                                        Tensor sse, Tensor count, Tensor? logw_out, Tensor? err) -> ()
 //
 // Replaces, like the C ABI below it (include/apgym_capi.h): SyncVectorEnv.reset/step over
 // TimeLimit(LIDARLocalization2DEnv) (ap_gym/envs/lidar_localization2d.py:293-389) and
@@ -606,6 +609,83 @@ void image_move(const at::Tensor &start, const at::Tensor &actions, double msl0,
         "apg_image_move");
 }
 
+// Overlap scores of target-position hypotheses from a localization env's own observations
+// (apg_image_overlap_scores).  glimpse, target_glimpse: float32 [M, s0, s1, C]; glimpse_pos: float64 or float32
+// [M, 2]; hypotheses: float64 or float32 [M, K, 2] or [K, 2] (shared by every set); image_size: H, W; logw, logw_out:
+// float32 [M, K], both or neither (logw_out may be logw itself); sse: float32 [M, K]; count: int32 [M, K]; err: int32
+// [1] or None.
+void image_overlap_scores(const at::Tensor &glimpse, const at::Tensor &glimpse_pos, const at::Tensor &target_glimpse,
+                          const at::Tensor &hypotheses, std::vector<int64_t> image_size, double sensor_scale,
+                          const c10::optional<at::Tensor> &logw, double gain, double tau, at::Tensor sse,
+                          at::Tensor count, const c10::optional<at::Tensor> &logw_out,
+                          const c10::optional<at::Tensor> &err) {
+  TORCH_CHECK(glimpse.is_cuda(), "glimpse must be on a GPU device, got ", glimpse.device());
+  const at::Device dev = glimpse.device();
+  const c10::DeviceGuard guard(dev);
+  TORCH_CHECK(glimpse.dim() == 4, "glimpse must be [M, s0, s1, C]");
+  TORCH_CHECK(image_size.size() == 2 && image_size[0] >= 2 && image_size[0] <= INT32_MAX && image_size[1] >= 2 &&
+                  image_size[1] <= INT32_MAX,
+              "image_size: (H, W), each >= 2");
+  const int64_t m = glimpse.size(0), s0 = glimpse.size(1), s1 = glimpse.size(2), ch = glimpse.size(3);
+  TORCH_CHECK(s0 >= 1 && s1 >= 1 && ch >= 1 && s0 <= 4096 && s1 <= 4096 && ch <= 4096 && s0 * s1 * ch <= 4096,
+              "a glimpse holds 1..4096 values, got ", s0, " x ", s1, " x ", ch);
+  const int64_t l = s0 * s1 * ch;
+  check_io(glimpse, dev, m * l, "glimpse");
+  check_io(target_glimpse, dev, m * l, "target_glimpse");
+  auto is_pos = [&](const at::Tensor &t) {
+    return t.device() == dev && t.is_contiguous() && (t.scalar_type() == at::kDouble || t.scalar_type() == at::kFloat);
+  };
+  TORCH_CHECK(is_pos(glimpse_pos) && glimpse_pos.numel() == 2 * m,
+              "glimpse_pos must be a contiguous float64 or float32 [M, 2] tensor on ", dev);
+  const bool shared = hypotheses.dim() == 2;
+  TORCH_CHECK((hypotheses.dim() == 3 && hypotheses.size(0) == m && hypotheses.size(2) == 2) ||
+                  (shared && hypotheses.size(1) == 2),
+              "hypotheses must be [M, K, 2] or [K, 2]");
+  TORCH_CHECK(is_pos(hypotheses), "hypotheses must be a contiguous float64 or float32 tensor on ", dev);
+  const int64_t k = hypotheses.size(shared ? 0 : 1);
+  TORCH_CHECK(k <= INT32_MAX, "hypotheses: too many per set");
+  apg_overlap_scores_args a{};
+  auto f32 = [&](const c10::optional<at::Tensor> &x, const char *name) -> float * {
+    if (!x.has_value() || !x->defined()) return nullptr;
+    check_io(*x, dev, m * k, name);
+    return reinterpret_cast<float *>(x->data_ptr());
+  };
+  a.logw = f32(logw, "logw");
+  a.logw_out = f32(logw_out, "logw_out");
+  TORCH_CHECK((logw.has_value() && logw->defined()) == (logw_out.has_value() && logw_out->defined()),
+              "logw and logw_out go together");
+  check_io(sse, dev, m * k, "sse");
+  TORCH_CHECK(count.device() == dev && count.scalar_type() == at::kInt && count.is_contiguous() &&
+                  count.numel() == m * k,
+              "count must be a contiguous int32 tensor of ", m * k, " elements on ", dev);
+  if (err.has_value() && err->defined()) {
+    TORCH_CHECK(err->device() == dev && err->scalar_type() == at::kInt && err->numel() == 1,
+                "err must be an int32 [1] tensor on ", dev);
+    a.err = reinterpret_cast<uint32_t *>(err->data_ptr());
+  }
+  if (m * k == 0) return;
+  a.glimpse = reinterpret_cast<const float *>(ptr(glimpse));
+  a.target_glimpse = reinterpret_cast<const float *>(ptr(target_glimpse));
+  a.glimpse_pos = ptr(glimpse_pos);
+  a.hypotheses = ptr(hypotheses);
+  a.sse = reinterpret_cast<float *>(ptr(sse));
+  a.count = reinterpret_cast<int32_t *>(ptr(count));
+  a.m = m;
+  a.k = (int32_t)k;
+  a.height = (int32_t)image_size[0];
+  a.width = (int32_t)image_size[1];
+  a.sensor_h = (int32_t)s0;
+  a.sensor_w = (int32_t)s1;
+  a.channels = (int32_t)ch;
+  a.pos_is_f32 = glimpse_pos.scalar_type() == at::kFloat;
+  a.hyp_is_f32 = hypotheses.scalar_type() == at::kFloat;
+  a.hyp_shared = shared;
+  a.gain = (float)gain;
+  a.tau = (float)tau;
+  a.sensor_scale = sensor_scale;
+  check(apg_image_overlap_scores(&a, stream_of(dev)), "apg_image_overlap_scores");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(apgym, m) {
@@ -642,4 +722,8 @@ TORCH_LIBRARY(apgym, m) {
   m.def("image_move(Tensor start, Tensor actions, float msl0, float msl1, int max_steps, Tensor(a!) pos, "
         "Tensor(b!) glimpse_pos, Tensor(c!) base_reward, Tensor(d!)? err) -> ()",
         image_move);
+  m.def("image_overlap_scores(Tensor glimpse, Tensor glimpse_pos, Tensor target_glimpse, Tensor hypotheses, "
+        "int[] image_size, float sensor_scale, Tensor? logw, float gain, float tau, Tensor(a!) sse, Tensor(b!) count, "
+        "Tensor(c!)? logw_out, Tensor(d!)? err) -> ()",
+        image_overlap_scores);
 }

@@ -51,6 +51,9 @@
  *   apg_image_glimpse_scores / apg_image_move
  *       the same glimpse at caller-chosen positions with a fused match score (image_perception_module.py:268-270's
  *       np.mean((a - b) ** 2)), and the module's move (:197-213) for candidate actions.
+ *   apg_image_overlap_scores / apg_image_overlap_chunk
+ *       nothing of the reference: how well a localization env's glimpse and target glimpse agree where the two
+ *       sensor windows would overlap under hypotheses of the target position, with a fused log-weight update.
  *   apg_image_unique_top_k
  *       ImagePerceptionModule.sample_unique_glimpse_positions  image_perception_module.py:253-277.
  *   apg_loss_ce / apg_loss_mse
@@ -94,7 +97,8 @@ extern "C" {
                                      (raised as IndexError) */
 #define APG_ERR_BAD_POSE 256u     /* apg_lidar_scan_poses / apg_lidar_move_poses: a pose (or a candidate action) with a
                                      non-finite coordinate; apg_lidar_pf_resample: a particle with such a pose or with a
-                                     NaN or +inf log-weight (raised as ValueError) */
+                                     NaN or +inf log-weight; apg_image_overlap_scores: a glimpse position or a
+                                     hypothesis with a non-finite coordinate (raised as ValueError) */
 
 #define APG_MAP_ROOMS 0
 #define APG_MAP_MAZE 1
@@ -657,6 +661,60 @@ int apg_image_glimpse_scores(const apg_image_config *cfg, const void *pool, cons
 int apg_image_move(const apg_image_config *cfg, const double *start, const float *actions, int64_t m, int32_t k,
                    int32_t t, int32_t max_steps, double *pos, float *glimpse_pos, float *base_reward, uint32_t *err,
                    apg_stream_t stream);
+
+/* Overlap scores of target-position hypotheses from what a localization agent itself observes (an addition to ABI
+ * 0.4; no changes to existing structs; nothing of the reference and no pool image is read).  For each set i of m:
+ * g = glimpse[i] (the agent's glimpse, taken at q = glimpse_pos[i]), G = target_glimpse[i] (the glimpse at the unknown
+ * target position) and k hypotheses h_j of that position.  The two sensor windows sample the same image, so where
+ * they overlap under hypothesis h, g must equal G resampled at the shift between the windows.  Every f32 and f64
+ * operation is rounded on its own, in the order written, with no fused multiply-add:
+ *   1 shift     d = ((f64(q) - f64(h)) * lim) / sensor_scale per component, lim = (lim_x, lim_y) the env's
+ *               sensor_pos_lim_pixels in f64 (lim_x = (width - 1) / 2 - (sensor_h * sensor_scale - 1) / 2,
+ *               lim_y = (height - 1) / 2 - (sensor_w * sensor_scale - 1) / 2: the reference's pairing, as the glimpse
+ *               kernels form it).  dy = d_y shifts axis 0 (index a, length s0 = sensor_h), dx = d_x axis 1 (index b,
+ *               length s1 = sensor_w): sample (a, b) of g lies at index coordinates (a + dy, b + dx) of G.
+ *   2 domain    a component of q or h that is not finite: sse = NaN, count = 0 and APG_ERR_BAD_POSE is OR-ed into
+ *               *err.  Otherwise, !(|dy| < s0) or !(|dx| < s1): sse = +0.0, count = 0, and nothing of g or G is read.
+ *   3 overlap   iy = floor(dy), fy = f32(dy - iy); ix, fx likewise.  Sample (a, b) is in the overlap iff
+ *               0 <= a + dy <= s0 - 1 and 0 <= b + dx <= s1 - 1, evaluated in f64.
+ *   4 error     in the overlap: r0 = a + iy, r1 = min(r0 + 1, s0 - 1), c0 = b + ix, c1 = min(c0 + 1, s1 - 1), and per
+ *               channel in f32
+ *                 top = G[r0][c0] * (1 - fx) + G[r0][c1] * fx
+ *                 bot = G[r1][c0] * (1 - fx) + G[r1][c1] * fx
+ *                 pred = top * (1 - fy) + bot * fy
+ *                 e = (g - pred) * (g - pred);
+ *               outside the overlap e = +0.0 (a NaN of g reaches only the hypotheses whose overlap contains it).
+ *   5 sums      sse[i][j] = numpy's f32 pairwise sum of the contiguous [s0][s1][C] block e (np.sum(e, dtype=float32));
+ *               count[i][j] = C * #(samples in the overlap).
+ *   6 belief    with logw: logw_out[i][j] = logw[i][j] + gain * (tau * f32(count) - sse), four f32 operations; NaN
+ *               where sse is not finite (apg_lidar_pf_resample treats NaN as a dead particle and flags it).  An
+ *               overlapping value that matches better than tau is evidence for the hypothesis, one that matches
+ *               worse evidence against it, a hypothesis without overlap keeps its weight.  logw_out may be exactly
+ *               logw (in place); logw NULL: no update (logw_out must be NULL too).
+ * hypotheses is [m][k][2], or with hyp_shared one [k][2] set used for every i.  Limits: L = s0 * s1 * C <= 4096
+ * (g and G of a workgroup live in LDS), k >= 0, m * ceil(k / chunk) < 2^31: APG_E_INVALID beyond.  m == 0 or k == 0
+ * launches nothing.  A workgroup takes one set and apg_image_overlap_chunk(m, k) consecutive hypotheses of it. */
+typedef struct apg_overlap_scores_args {
+  const float *glimpse;        /* [m][s0][s1][C] */
+  const float *target_glimpse; /* [m][s0][s1][C] */
+  const void *glimpse_pos;     /* [m][2] (x, y), f64 or f32 (pos_is_f32) */
+  const void *hypotheses;      /* [m][k][2] ([k][2] with hyp_shared) (x, y), f64 or f32 (hyp_is_f32) */
+  const float *logw;           /* [m][k] or NULL */
+  float *sse;                  /* [m][k] */
+  int32_t *count;              /* [m][k] */
+  float *logw_out;             /* [m][k] with logw, else NULL; may be logw */
+  uint32_t *err;               /* or NULL */
+  int64_t m;
+  int32_t k;
+  int32_t height, width;       /* image_size */
+  int32_t sensor_h, sensor_w, channels;
+  int32_t pos_is_f32, hyp_is_f32, hyp_shared;
+  float gain, tau;
+  double sensor_scale;
+} apg_overlap_scores_args;
+int apg_image_overlap_scores(const apg_overlap_scores_args *args, apg_stream_t stream);
+/* Hypotheses per workgroup of apg_image_overlap_scores for m sets of k (a power of two in 8..64; 0 for m or k <= 0). */
+int32_t apg_image_overlap_chunk(int64_t m, int32_t k);
 
 /* Uniqueness ranking of sample_unique_glimpse_positions: top_k[N][k] grid indices by descending
  * min_{b != a} mean((g_b - g_a)^2) (exact ties: ascending index); uniq[N][P] (float, may be NULL). */
