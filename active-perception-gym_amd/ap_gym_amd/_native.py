@@ -239,6 +239,9 @@ SYMBOLS = [
     ("apg_version", ctypes.c_char_p, []),
     ("apg_last_error", ctypes.c_char_p, []),
     ("apg_lidar_query_sizes", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarSizes)]),
+    ("apg_lidar_window_cache_bytes", ctypes.c_size_t, [ctypes.POINTER(LidarConfig)]),
+    ("apg_lidar_window_cache_zone", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("apg_lidar_init", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), _vp]),
     ("apg_lidar_reset", ctypes.c_int, [ctypes.POINTER(LidarConfig), ctypes.POINTER(LidarState), ctypes.c_uint64,
                                        ctypes.c_int, ctypes.POINTER(LidarOutputs), _vp]),

@@ -304,6 +304,7 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
         L = N.lib()
         sizes = N.LidarSizes()
         N.check(L.apg_lidar_query_sizes(ctypes.byref(self._cfg), ctypes.byref(sizes)), "apg_lidar_query_sizes")
+        wc_bytes = int(L.apg_lidar_window_cache_bytes(ctypes.byref(self._cfg)))
 
         dev, n, B = self.device, self.num_envs, self.lidar_beam_count
         t = torch
@@ -315,7 +316,9 @@ class LIDARLocalization2DVectorEnv(VectorEnv):
             rng=t.zeros((n, 5), dtype=t.int64, device=dev),
             it_rng=t.zeros((n, 5), dtype=t.int64, device=dev),
             occ=t.zeros(max(1, sizes.occ_bytes // 8), dtype=t.int64, device=dev),
-            scratch=t.zeros(sizes.scratch_bytes // 8, dtype=t.int64, device=dev) if sizes.scratch_bytes else None,
+            # the step kernel's resident window cache (rows int32 [n, 32], then n origin words; zero: no valid
+            # origin), None for the configurations that step without one
+            scratch=t.zeros(wc_bytes // 4, dtype=t.int32, device=dev) if wc_bytes else None,
             stack=t.zeros(sizes.stack_bytes // 2, dtype=t.int16, device=dev) if sizes.stack_bytes else None,
             map_idx=t.full((n,), int(static_map_index) if self.static_map else 0, dtype=t.int64, device=dev),
             beam_dirs=t.as_tensor(lidar_beam_directions(B, lidar_range), device=dev),

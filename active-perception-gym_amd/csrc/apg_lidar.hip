@@ -827,7 +827,42 @@ struct StepParams {
                 // ~98 % of the beams touch a wall, the pre-test only delays them)
   int p4;       // the pre-test reads a 4-row OR table of the windows (built by phase 1's idle waves; step_lds_bytes)
   float range, loss_scale, loss_offset;
+  uint32_t *wc;  // the resident window cache (apg_lidar_state.scratch; WinCache below), or NULL: windows from occ
 };
+
+// The window cache: each env's staged 32 x 32 window kept in HBM between steps (apg_lidar_window_cache_bytes), so an
+// ordinary step reads 128 contiguous, position-independent bytes per env instead of gathering rows out of `occ` at
+// an address that depends on `pos`.  Layout: rows u32 [N][32], then one origin word per env,
+// WC_VALID | (y0 + 64) << 12 | (x0 + 64) (zeroed memory: no valid origin).  The window floats: it is re-centred
+// (origin floor(pos) - 15) only when the env nears the edge of the zone below, or resets.
+//   Hard zone: the offsets o = floor(pos) - origin of the pre-move position for which everything a step can touch
+// lies inside the window.  By the reasoning of P.wlo / P.whi (launch_step_kernel) a step reads map rows
+// floor(pos.y) - (R + 7) .. floor(pos.y) + (R + 7) (the scans' cells within R + 5, two more rows of the walk's
+// read-ahead, which columns do not have) and columns floor(pos.x) - (R + 5) .. floor(pos.x) + (R + 5) (the quad
+// reads' extra column included), so o.y in [R + 7, 24 - R] and o.x in [R + 5, 26 - R].  (RowsWindow::or_rows' reads
+// past its last row are masked off and land in the LDS padding, wherever the box lies.)
+//   Inner zone: the hard zone shrunk by WC_DRIFT = 2, a bound on the change of floor(pos) per step and axis: a step
+// adds the move, dir * d with |dir| <= 1 and d <= total <= 1 (the action is clamped to length 1, up to f32 rounding),
+// and the slide, at most rem = total - d along one axis, so the exact displacement is at most 1 + a few ulp; each
+// of the two f32 additions rounds by at most half an ulp of a value below 512 (2^-15), and np.clip only moves the
+// result towards the old position's side.  |pos' - pos| < 2 gives |floor(pos') - floor(pos)| <= 2 (1 is what
+// replays show: the f32 sum can round up to the next integer, which alone would allow 2).  An env whose pre-move
+// position is inside the inner zone therefore starts the next step inside the hard zone; the others are re-centred
+// during the step.  The bound is not load-bearing for the results: every step checks the hard zone of every env of
+// a workgroup before it uses the cached windows.
+constexpr uint32_t WC_VALID = 0x80000000u;
+constexpr int WC_DRIFT = 2;
+struct WinZone {
+  int xlo, xhi, ylo, yhi;  // inclusive
+  __host__ __device__ bool holds(int ox, int oy) const { return ox >= xlo && ox <= xhi && oy >= ylo && oy <= yhi; }
+  __host__ __device__ bool empty() const { return xlo > xhi || ylo > yhi; }
+};
+__host__ __device__ inline WinZone wc_zone(int R, int shrink) {
+  return WinZone{R + 5 + shrink, 26 - R - shrink, R + 7 + shrink, 24 - R - shrink};
+}
+__host__ __device__ inline uint32_t wc_origin_word(int x0, int y0) {
+  return WC_VALID | (uint32_t)(y0 + 64) << 12 | (uint32_t)(x0 + 64);
+}
 
 // ActiveRegressionLogWrapper (active_regression_env.py:131-159): per step |target - prediction| and
 // mean((target - prediction)^2) in float32; at the episode end avg = float(np.mean(list)) (numpy's
@@ -879,6 +914,25 @@ __device__ unsigned long long g_step_prof_w[16384][16][2];
 #else
 #define STEP_MARK(k)
 #define STEP_MARK_W(k)
+#endif
+#ifdef APG_TIMING_DENSE_WIN
+// Timing builds only (the ceiling of keeping the staged windows resident across steps, profiles/r07): the step reads
+// its 32 staged rows per env from this dense buffer, position-independent and fully coalesced, instead of gathering
+// them from `occ` at `pos`.  k_timing_fill_win, launched in front of every step, stores the windows into it, so the
+// later phases do their usual work; only reset steps are wrong (they stage the windows of before the reset).
+constexpr int TIMING_WIN_ENVS = 1 << 18;
+__device__ uint32_t g_timing_win[(size_t)TIMING_WIN_ENVS * MAX_WIN_ROWS];
+__global__ __launch_bounds__(256) void k_timing_fill_win(StepParams P, apg_lidar_state S) {
+  const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int e = (int)(r / MAX_WIN_ROWS), row = (int)(r % MAX_WIN_ROWS);
+  if (e >= P.n || e >= TIMING_WIN_ENVS) return;
+  uint32_t v = 0;
+  const int y = (int)floorf(S.pos[2 * e + 1]) - 15 + row;
+  if (row >= P.wlo && row < P.whi && (unsigned)y < (unsigned)P.h)
+    v = extract_window_row(S.occ + (P.is_static ? 0 : (size_t)e * P.h * P.wpr) + (size_t)y * P.wpr, P.wpr,
+                           (int)floorf(S.pos[2 * e]) - 15);
+  g_timing_win[r] = v;
+}
 #endif
 #ifndef APG_SLIDE_SPLIT
 #define APG_SLIDE_SPLIT 1  // phase 1: second slide scan on the idle waves (0: both on the env's lane; A/B 36.4 -> 35.8 us)
@@ -990,7 +1044,8 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
   __shared__ int s_x0[EPB], s_y0[EPB];
   __shared__ uint16_t s_rlist[EPB];  // envs that reset this step (map obs pass)
   __shared__ uint32_t s_start[EPB];  // rooms autoreset: start cell y << 8 | x, or ~0u (no free cell)
-  __shared__ int s_cnt[4];           // 0: reset-list length, 1: queued walks, 2: walk / chunk cursor
+  __shared__ int s_cnt[4];           // 0: reset-list length, 1: queued walks, 2: walk / chunk cursor, 3: s_wlist length
+  __shared__ uint32_t s_wlist[EPB];  // window cache: envs to re-centre, new origin (low 24 bits) << 8 | env slot
   __shared__ float s_dirs[MAX_STAGED_BEAMS][2];  // beam_dirs, read inside the beam loops (LDS, not HBM latency)
 #if APG_SLIDE_SPLIT
   __shared__ float s_slide[EPB];  // phase 1: the second slide candidate's length, then its scan distance
@@ -1063,6 +1118,14 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
   constexpr int WIN_ITERS = EPB * MAX_WIN_ROWS / T;
   uint32_t wv[WIN_ITERS];
   auto load_windows = [&]() {
+#ifdef APG_TIMING_DENSE_WIN  // timing experiment only (stale windows): the staged rows from a dense per-env buffer
+#pragma unroll
+    for (int k = 0; k < WIN_ITERS; k++) {
+      const size_t r = (size_t)base * MAX_WIN_ROWS + tid + k * T;
+      wv[k] = r < (size_t)TIMING_WIN_ENVS * MAX_WIN_ROWS ? g_timing_win[r] : 0u;
+    }
+    return;
+#endif
 #pragma unroll
     for (int k = 0; k < WIN_ITERS; k++) {
       const int r = tid + k * T;
@@ -1081,10 +1144,40 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
       }
     }
   };
-  if constexpr (!GR) load_windows();
+  // With the window cache (WinCache above) the prologue reads the workgroup's cached rows, one contiguous block
+  // that depends on nothing loaded, and the owners their origin words.  wc_fb ("fall back"): some env of the
+  // workgroup has no valid origin, resets at this step, or starts outside the hard zone; the workgroup then stages
+  // today's windows (after phase R) and writes all its rows and origins back, so its next step is warm.
+  uint32_t *const wc = GR ? nullptr : P.wc;
+  bool wc_bad = false;
+  if (wc) {
+#pragma unroll
+    for (int k = 0; k < WIN_ITERS; k++) {
+      const int r = tid + k * T;
+      wv[k] = base + r / MAX_WIN_ROWS < P.n ? wc[(size_t)base * MAX_WIN_ROWS + r] : 0u;
+    }
+    if (own) {
+      const uint32_t org = wc[(size_t)P.n * MAX_WIN_ROWS + oe];
+      const int x0 = (int)(org & 0xFFFu) - 64, y0 = (int)((org >> 12) & 0xFFFu) - 64;
+      s_x0[tid] = x0;  // kept in LDS, not in a register across phase R (phase 0 overwrites them on a fallback)
+      s_y0[tid] = y0;
+      wc_bad = !(org & WC_VALID) || (pf_f & (F_AUTORESET | F_JUST_RESET)) ||
+               !wc_zone(P.R, 0).holds((int)floorf(pf_px) - x0, (int)floorf(pf_py) - y0);
+    }
+  } else if constexpr (!GR) {
+    load_windows();
+  }
   const bool dir_thread = P.beams <= MAX_STAGED_BEAMS && tid < 2 * P.beams;
   const float dir_v = dir_thread ? S.beam_dirs[tid] : 0.0f;
-  if constexpr (!FUSED) __syncthreads();
+  bool wc_fb = true;
+  if constexpr (!FUSED) {
+    if (wc) {
+      wc_fb = __syncthreads_or(wc_bad);
+      if (wc_fb) load_windows();
+    } else {
+      __syncthreads();
+    }
+  }
 
   // ---------------- phase R: NEXT_STEP autoresets (fused instances), env-major.  The barrier of
   // __syncthreads_or also publishes the counters above.
@@ -1096,6 +1189,7 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
       // the step's reset count to the prefetcher (pinned host word): every workgroup adds its count, the last one
       // to finish this point (ticket) publishes the total and rearms the counters for the next step
       npend = __syncthreads_count(pend);
+      if (wc) wc_fb = npend || __syncthreads_or(wc_bad);  // (a pending env's owner has wc_bad set)
       if (tid == 0) {  // (coherent relaxed atomics, ordered by a vmcnt wait instead of a release fence's L2 flush)
         if (npend) __hip_atomic_fetch_add(&V.ctl[1], (unsigned long long)npend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the count is added before the ticket is taken
@@ -1107,6 +1201,9 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
           __hip_atomic_store(&V.ctl[2], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
+    } else if (wc) {  // one vote on the ordinary step; the rare workgroup that falls back then asks why
+      wc_fb = __syncthreads_or(pend || wc_bad);
+      npend = wc_fb ? __syncthreads_or(pend) : 0;
     } else {
       npend = __syncthreads_or(pend);
     }
@@ -1404,6 +1501,8 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
         pf_el = S.elapsed[oe];
       }
       if constexpr (!GR) load_windows();  // the reset envs' new maps and positions
+    } else if (wc && wc_fb) {
+      load_windows();
     }
   }
 
@@ -1411,8 +1510,16 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
   if (dir_thread) s_dirs[tid >> 1][tid & 1] = dir_v;
   constexpr bool kMapObsHere = !(FUSED && (GEN == GEN_ROOMS || GEN == GEN_PF));  // fused resets wrote it in phase R
   if (own) {
-    s_x0[tid] = (int)floorf(pf_px) - 15;
-    s_y0[tid] = (int)floorf(pf_py) - 15;
+    const int cx0 = (int)floorf(pf_px) - 15, cy0 = (int)floorf(pf_py) - 15;  // the centred origin
+    if (wc_fb) {
+      s_x0[tid] = cx0;
+      s_y0[tid] = cy0;
+      if (wc) wc[(size_t)P.n * MAX_WIN_ROWS + oe] = wc_origin_word(cx0, cy0);
+    } else {  // the cached origin stands (prologue); an env outside the inner zone is listed for phase 1
+      const int x0 = s_x0[tid], y0 = s_y0[tid];
+      if (!wc_zone(P.R, WC_DRIFT).holds(cx0 + 15 - x0, cy0 + 15 - y0))
+        s_wlist[atomicAdd(&s_cnt[3], 1)] = wc_origin_word(cx0, cy0) << 8 | (uint32_t)tid;
+    }
     if (kMapObsHere && (pf_f & F_JUST_RESET)) s_rlist[atomicAdd(&s_cnt[0], 1)] = (uint16_t)tid;
   }
   if constexpr (kMapObsHere) __syncthreads();
@@ -1460,6 +1567,7 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
       const int r = tid + k * T;
       const int el = r / MAX_WIN_ROWS, row = r - el * MAX_WIN_ROWS;
       s_win[el * WIN_STRIDE + row] = wv[k];
+      if (wc && wc_fb && base + el < P.n) wc[(size_t)base * MAX_WIN_ROWS + r] = wv[k];  // the next step's rows
     }
   }
   STEP_MARK(9)
@@ -1536,6 +1644,22 @@ __global__ __launch_bounds__(4 * EPB, APG_STEP_MIN_WAVES) void k_lidar_step(Step
         b = c;
         c = d;
       }
+    }
+  }
+  if (wc && !wc_fb && tid >= 2 * EPB) {
+    // the same waves re-centre the windows of the listed envs for the NEXT step: 32 lanes per env extract its rows
+    // at the new origin from occ and store them and the origin to the cache.  This step keeps the window it staged
+    // (the env started inside the hard zone), and nothing reads the cache again within the launch.
+    const int nl = s_cnt[3];
+    for (int i = (tid - 2 * EPB) >> 5; i < nl; i += (T - 2 * EPB) >> 5) {
+      const uint32_t ent = s_wlist[i], org = ent >> 8;
+      const int re = base + (int)(ent & 255u), row = tid & 31;
+      const int x0 = (int)(org & 0xFFFu) - 64, y = (int)((org >> 12) & 0xFFFu) - 64 + row;
+      uint32_t v = 0;
+      if ((unsigned)y < (unsigned)P.h)
+        v = extract_window_row(S.occ + (P.is_static ? 0 : (size_t)re * words) + (size_t)y * P.wpr, P.wpr, x0);
+      wc[(size_t)re * MAX_WIN_ROWS + row] = v;
+      if (row == 0) wc[(size_t)P.n * MAX_WIN_ROWS + re] = WC_VALID | org;
     }
   }
 #if APG_SLIDE_SPLIT
@@ -2121,6 +2245,14 @@ bool pf_supported(const apg_lidar_config *c) {
          (int)ceilf(c->lidar_range) <= MAX_WIN_RANGE;
 }
 
+// Bytes of the window cache (apg_lidar_window_cache_bytes): rows and origin words, for the staged-window step
+// instances whose inner zone is not empty (lidar_range <= 6); 0: the configuration steps without a cache.
+size_t wc_bytes(const apg_lidar_config *c) {
+  const int R = (int)ceilf(c->lidar_range);
+  if (c->num_envs <= 0 || R < 0 || R > MAX_WIN_RANGE || wc_zone(R, WC_DRIFT).empty()) return 0;
+  return (size_t)c->num_envs * (MAX_WIN_ROWS + 1) * sizeof(uint32_t);
+}
+
 int cu_count() {
   static int cus = 0;
   if (cus == 0) {
@@ -2213,6 +2345,13 @@ int launch_step_kernel(const apg_lidar_config *cfg, const apg_lidar_state *st, c
   // of its scans, plus two rows for the walk's one-crossing-ahead row reads past the segment's end
   P.wlo = std::max(0, 15 - (P.R + 5) - 2);
   P.whi = std::min(MAX_WIN_ROWS, 15 + (P.R + 5) + 2 + 1);
+  // the window cache (WinCache): APG_STEP_WINCACHE=0 forces the uncached path (A/B and parity runs)
+  static const int wc_knob = getenv("APG_STEP_WINCACHE") ? atoi(getenv("APG_STEP_WINCACHE")) : 1;
+  P.wc = wc_knob && wc_bytes(cfg) ? reinterpret_cast<uint32_t *>(st->scratch) : nullptr;
+  if (P.wc) {  // a floating origin: the needed rows can be any of the window's
+    P.wlo = 0;
+    P.whi = MAX_WIN_ROWS;
+  }
   static int forced_pt = -2;  // APG_STEP_PRETEST=0|1 (tuning A/B only: the outputs do not depend on it)
   if (forced_pt == -2) {
     const char *e = getenv("APG_STEP_PRETEST");
@@ -2225,6 +2364,13 @@ int launch_step_kernel(const apg_lidar_config *cfg, const apg_lidar_state *st, c
   P.loss_offset = cfg->loss_offset;
   const Geo g = make_geo(cfg);
   int rc;
+#ifdef APG_TIMING_DENSE_WIN
+  // the dense buffer is rebuilt before every step (stale windows let envs walk off their maps, and the resulting
+  // autoresets dominate the kernel); reset steps still stage the pre-reset windows
+  if (P.R <= MAX_WIN_RANGE) {
+    hipLaunchKernelGGL(k_timing_fill_win, dim3(grid_for(std::min(P.n, TIMING_WIN_ENVS) * MAX_WIN_ROWS, 256)), dim3(256), 0, s, P, *st);
+  }
+#endif
   switch (step_epb(P.n)) {
     case 256: rc = launch_step_epb<256>(P, g, st, act, pred, out, s, fused, pf); break;
     default: rc = launch_step_epb<64>(P, g, st, act, pred, out, s, fused, pf); break;
@@ -2446,6 +2592,24 @@ int apg_lidar_query_sizes(const apg_lidar_config *cfg, apg_lidar_state_sizes *o)
   o->stack_bytes = g.kind == APG_MAP_MAZE ? (size_t)g.frames * (g.is_static ? 1 : (size_t)g.n) * sizeof(uint16_t) : 0;
   // (maze scratch: apg_maze.hpp's carve log + spilled DFS frames, maze_frames u16 per map)
   o->prefetch_bytes = pf_supported(cfg) ? pf_layout(g.n, g.h, g.wpr).bytes : 0;
+  return APG_OK;
+}
+
+size_t apg_lidar_window_cache_bytes(const apg_lidar_config *cfg) {
+  if (!cfg || validate(cfg)) return 0;
+  return wc_bytes(cfg);
+}
+
+int apg_lidar_window_cache_zone(const apg_lidar_config *cfg, int inner, int32_t zone[4], int32_t *max_drift) {
+  if (!cfg || !zone) return fail(APG_E_INVALID, "null argument");
+  if (int rc = validate(cfg)) return rc;
+  if (!wc_bytes(cfg)) return fail(APG_E_INVALID, "this configuration has no window cache");
+  const WinZone z = wc_zone((int)ceilf(cfg->lidar_range), inner ? WC_DRIFT : 0);
+  zone[0] = z.xlo;
+  zone[1] = z.xhi;
+  zone[2] = z.ylo;
+  zone[3] = z.yhi;
+  if (max_drift) *max_drift = WC_DRIFT;
   return APG_OK;
 }
 

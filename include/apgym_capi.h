@@ -163,7 +163,8 @@ typedef struct apg_lidar_state {
   apg_pcg64 *rng;      /* [N]   env np_random */
   apg_pcg64 *it_rng;   /* [N]   DatasetIterator rng (dynamic maps) */
   uint64_t *occ;       /* [N or 1][H][wpr] bit-packed occupancy, wpr = ceil(W/64) */
-  uint64_t *scratch;   /* reserved, unused (may be NULL; query_sizes reports scratch_bytes = 0) */
+  uint64_t *scratch;   /* NULL, or apg_lidar_window_cache_bytes() of zeroed memory: the step's window cache
+                          (query_sizes reports scratch_bytes = 0) */
   uint16_t *stack;     /* [N or 1][maze_frames] maze scratch (carve log + spilled DFS frames), contiguous
                           per map, 64-byte aligned (mazes only) */
   uint64_t *map_idx;   /* [N]   dataset index of the current map */
@@ -214,6 +215,21 @@ const char *apg_version(void);
 const char *apg_last_error(void);
 
 int apg_lidar_query_sizes(const apg_lidar_config *cfg, apg_lidar_state_sizes *out);
+
+/* Bytes of the step's resident window cache for this configuration, or 0 when it steps without one (lidar_range
+ * above 6).  A caller may pass that many bytes of ZEROED device memory (4-byte aligned) as apg_lidar_state.scratch:
+ * the step kernel then keeps each env's staged 32 x 32 occupancy window there between steps (u32 rows [N][32], then
+ * one origin word per env: bit 31 valid, (y0 + 64) << 12 | (x0 + 64)) and re-centres it only when the env drifts or
+ * resets.  scratch == NULL steps exactly as before; the outputs are the same either way.  The buffer belongs to the
+ * step kernel: every other writer of occ / pos (resets, map installs) leaves the env's F_JUST_RESET flag set, which
+ * makes the next step rebuild the env's workgroup.  A caller that rewrites occ or pos itself must zero the origin
+ * words.  (apg_lidar_query_sizes keeps scratch_bytes = 0.) */
+size_t apg_lidar_window_cache_bytes(const apg_lidar_config *cfg);
+/* The cache's zones as inclusive offsets floor(pos) - origin, zone = {x_lo, x_hi, y_lo, y_hi}: the hard zone
+ * (inner = 0: a step may use a cached window only for a pre-move position inside it) or the inner zone (inner = 1: the
+ * hard zone shrunk by *max_drift, the bound on the change of floor(pos) per step and axis; an env outside it is
+ * re-centred during the step).  Host-only.  APG_E_INVALID for a configuration without a cache. */
+int apg_lidar_window_cache_zone(const apg_lidar_config *cfg, int inner, int32_t zone[4], int32_t *max_drift);
 
 /* Build the static map (is_static) into state->occ; no-op for dynamic maps. */
 int apg_lidar_init(const apg_lidar_config *cfg, const apg_lidar_state *st, apg_stream_t stream);
