@@ -251,6 +251,9 @@ APG_DEV void geos_intersection(double p1x_, double p1y_, double p2x_, double p2y
 APG_DEV float f32_div(float a, float b) { return (float)__ddiv_rn((double)a, (double)b); }
 APG_DEV float f32_sqrt(float a) { return (float)__dsqrt_rn((double)a); }
 
+// np.clip(x, lo, hi) for finite lo <= hi: a NaN x stays NaN (fminf / fmaxf would return the bound instead).
+APG_DEV float f32_clip(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
 // a / b for a divisor fixed per launch, from inv = 1.0 / (double)b (correctly rounded f64): the f64
 // product is within 2^-52 (relative) of a / b, while a quotient of two f32 values is never an f32
 // rounding midpoint (odd 25-bit x 24-bit significands need >= 25 bits) and, when not one, lies >= 2^-49

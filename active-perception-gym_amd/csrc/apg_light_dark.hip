@@ -148,8 +148,8 @@ APG_DEV void noisy_obs(Pcg64 &r, float px, float py, float *out) {
   const float z0 = (float)__dadd_rn(0.0, __dmul_rn(1.0, standard_normal(r)));
   const float z1 = (float)__dadd_rn(0.0, __dmul_rn(1.0, standard_normal(r)));
   const float s = light_std(px, py);
-  out[0] = fminf(fmaxf(__fadd_rn(px, __fmul_rn(z0, s)), -2.0f), 2.0f);
-  out[1] = fminf(fmaxf(__fadd_rn(py, __fmul_rn(z1, s)), -2.0f), 2.0f);
+  out[0] = f32_clip(__fadd_rn(px, __fmul_rn(z0, s)), -2.0f, 2.0f);  // NaN (a NaN position) stays NaN, as in np.clip
+  out[1] = f32_clip(__fadd_rn(py, __fmul_rn(z1, s)), -2.0f, 2.0f);
 }
 
 // reset (:106-118): pos = uniform(-ones(2), ones(2), size=2).astype(float32), then the observation
@@ -234,8 +234,9 @@ __global__ __launch_bounds__(256) void k_light_dark_step(apg_light_dark_config c
   px = __fadd_rn(px, __fmul_rn(ax, 0.15f));
   py = __fadd_rn(py, __fmul_rn(ay, 0.15f));
   bool term = fabsf(px) >= 1.0f || fabsf(py) >= 1.0f;
-  px = fminf(fmaxf(px, -1.0f), 1.0f);
-  py = fminf(fmaxf(py, -1.0f), 1.0f);
+  // np.clip: an infinite action component gives inf / inf = NaN, and the position stays NaN until the time limit
+  px = f32_clip(px, -1.0f, 1.0f);
+  py = f32_clip(py, -1.0f, 1.0f);
   Pcg64 r = *reinterpret_cast<const Pcg64 *>(&S.rng[e]);
   float obs[2];
   noisy_obs(r, px, py, obs);

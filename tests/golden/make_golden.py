@@ -19,6 +19,8 @@ Sources of truth, per fixture:
                    small synthetic uint8 pools (image_cls_f32rgb, image_loc_f64gray3: float pools in
                    [-0.2, 1.2]; HF datasets are not available offline), seeded through
                    the gymnasium VectorEnv.reset restatement in tests/golden/_stubs.
+  *_edges.npz, light_dark_limit300.npz   (section "edges") the same envs stepped with the edge-action schedule
+                   of tests/edge_actions.py, and LightDark at max_episode_steps=300.
 The fixtures hold data only (inputs and expected outputs).  See DESIGN.md §Oracle for what each pins.
 """
 
@@ -188,6 +190,7 @@ def _reset_prediction_info_shim(ap):
 
 def run_lidar_env(name, dataset, static, beams, n_envs, steps, seed, action_mode, sparse=False, static_map_index=0,
                   extra=None, lidar_range=5):
+    """action_mode: "uniform", "wide", "grid", or an explicit float32 [steps, n_envs, 2] action array."""
     lmod = _lidar_module()
     gym = sys.modules["gymnasium"]
     ap = sys.modules["ap_gym"]
@@ -204,7 +207,10 @@ def run_lidar_env(name, dataset, static, beams, n_envs, steps, seed, action_mode
     venv = gym.vector.SyncVectorEnv([mk for _ in range(n_envs)])
     obs, info = venv.reset(seed=seed)
     arng = np.random.default_rng(1)
-    if action_mode == "uniform":
+    if not isinstance(action_mode, str):
+        actions = np.asarray(action_mode, np.float32)
+        assert actions.shape == (steps, n_envs, 2)
+    elif action_mode == "uniform":
         actions = arng.uniform(-1, 1, (steps, n_envs, 2)).astype(np.float32)
     elif action_mode == "wide":
         actions = arng.uniform(-2.5, 2.5, (steps, n_envs, 2)).astype(np.float32)
@@ -385,7 +391,8 @@ def _image_modules():
 
 
 def run_image_env(name, kind, pool_shape, channels, num_classes, sensor, scale, step_limit, invert, n_envs,
-                  steps, seed, pool_len, pool_seed, sparse=False, pool_dtype=np.uint8, pool_range=(-0.2, 1.2)):
+                  steps, seed, pool_len, pool_seed, sparse=False, pool_dtype=np.uint8, pool_range=(-0.2, 1.2),
+                  actions=None):
     ipm, icd, ic, il = _image_modules()
     prng = np.random.default_rng(pool_seed)
     if pool_dtype == np.uint8:
@@ -420,15 +427,18 @@ def run_image_env(name, kind, pool_shape, channels, num_classes, sensor, scale, 
            "config": np.array([pool_shape[0], pool_shape[1], channels, num_classes, sensor[0], sensor[1],
                                step_limit, int(invert), n_envs, steps], np.int64),
            "sensor_scale": np.array(scale, np.float64), "kind": np.array(kind)}
-    _trace_image_env(env, kind, n_envs, num_classes, steps, seed, sparse, out)
+    _trace_image_env(env, kind, n_envs, num_classes, steps, seed, sparse, out, actions=actions)
     save(f"image_{name}.npz", **out)
 
 
-def _trace_image_env(env, kind, n_envs, num_classes, steps, seed, sparse, out, mask_prediction=False):
-    """Reset with `seed`, step with seeded actions/predictions, record every output into `out`."""
+def _trace_image_env(env, kind, n_envs, num_classes, steps, seed, sparse, out, mask_prediction=False, actions=None):
+    """Reset with `seed`, step with seeded actions/predictions (or the given actions), record every output into
+    `out`."""
     obs, info = env.reset(seed=seed)
     arng = np.random.default_rng(11)
-    actions = arng.uniform(-1.5, 1.5, (steps, n_envs, 2)).astype(np.float32)
+    uniform = arng.uniform(-1.5, 1.5, (steps, n_envs, 2)).astype(np.float32)
+    actions = uniform if actions is None else np.asarray(actions, np.float32)
+    assert actions.shape == (steps, n_envs, 2)
     if kind == "cls":
         preds = arng.standard_normal((steps, n_envs, num_classes)).astype(np.float32)
     else:
@@ -588,23 +598,29 @@ def make_circle_square():
 
 
 # --------------------------------------------------------------------------- LightDark
-def run_light_dark(name, n_envs, steps, seed, action_scale, sparse=False):
+def run_light_dark(name, n_envs, steps, seed, action_scale, sparse=False, max_episode_steps=50, actions=None):
     """LightDark-v0 as registered (registration.py:640-647): TimeLimit(50, issue_termination=True) +
-    ActiveRegressionLogWrapper over LightDarkEnv, vectorised by the SyncVectorEnv restatement."""
+    ActiveRegressionLogWrapper over LightDarkEnv, vectorised by the SyncVectorEnv restatement.
+    action_scale: a scalar, or one scale per env; `actions`: an explicit float32 [steps, n_envs, 2] array instead.
+    A max_episode_steps other than the registered 50 is stored in the fixture."""
     ap = refload.load_core()
     ld = refload.load("envs.light_dark")
     gym = sys.modules["gymnasium"]
     sw = refload.load("sparsify_wrapper") if sparse else None
 
     def mk():
-        env = ap.TimeLimit(ld.LightDarkEnv(), max_episode_steps=50, issue_termination=True)
+        env = ap.TimeLimit(ld.LightDarkEnv(), max_episode_steps=max_episode_steps, issue_termination=True)
         env = ap.ActiveRegressionLogWrapper(env)
         return sw.SparsifyWrapper(_reset_prediction_info_shim(ap)(env)) if sparse else env
 
     venv = gym.vector.SyncVectorEnv([mk for _ in range(n_envs)])
     obs, info = venv.reset(seed=seed)
     arng = np.random.default_rng(2)
-    actions = arng.uniform(-action_scale, action_scale, (steps, n_envs, 2)).astype(np.float32)
+    if actions is None:
+        scale = action_scale if np.ndim(action_scale) == 0 else np.asarray(action_scale, np.float64)[None, :, None]
+        actions = arng.uniform(-scale, scale, (steps, n_envs, 2)).astype(np.float32)
+    actions = np.asarray(actions, np.float32)
+    assert actions.shape == (steps, n_envs, 2)
     preds = arng.uniform(-1, 1, (steps, n_envs, 2)).astype(np.float32)
     if sparse:
         preds[5::7, 0] = np.float32(1e20)
@@ -650,7 +666,10 @@ def run_light_dark(name, n_envs, steps, seed, action_scale, sparse=False):
     for key, v in vec.items():
         out["stats_vector_" + key] = np.array(v, np.float32)
     out["reward_dtype"] = np.array(str(rew.dtype))
+    if max_episode_steps != 50:
+        out["max_episode_steps"] = np.array(max_episode_steps)
     save(f"light_dark_{name}.npz", **out)
+    return out
 
 
 def make_light_dark():
@@ -1058,12 +1077,44 @@ def make_lidar_long():
     run_lidar_env("pool72_r28_b8_grid", ds, False, 8, 5, 105, 8, "grid", extra=extra, lidar_range=28)
 
 
+def make_edges():
+    """Edge actions (tests/edge_actions.py) and LightDark episodes up to a limit of 300: new files only.
+      light_dark_edges      non-finite actions leave a NaN position until the time limit, then the autoreset
+      light_dark_limit300   per-env action scales: some episodes run to the limit, some leave the square early
+      lidar_env_rooms32_b8_edges, image_loc_edges (no non-finite rows: a NaN glimpse position would go through
+      scipy's float-to-int cast, which is undefined)"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import edge_actions as ea
+
+    acts = ea.edge_schedule(120, 8, 31, scale=1.0, nonfinite=12)
+    out = run_light_dark("edges", 8, 120, 11, None, actions=acts)
+    stepped, term = out["step_info_mask"], out["step_terminated"]
+    print("light_dark_edges", ea.assert_edges_hit(acts, stepped), "followups",
+          ea.nonfinite_followups(acts, stepped, term))
+    assert ea.nonfinite_followups(acts, stepped, term) >= 3
+    nanpos = np.isnan(out["step_noisy_position"]).any(-1)
+    assert (nanpos[:-1] & term[:-1] & ~stepped[1:]).any()  # a NaN episode ran to the limit and autoreset
+    out = run_light_dark("limit300", 6, 620, 21, [0.02, 0.05, 0.15, 0.4, 0.8, 1.5], max_episode_steps=300)
+    lens = out["step_stats_len"][out["step_stats_len"] > 0]
+    print("light_dark_limit300 episode lengths", sorted(lens.tolist()))
+    assert (lens == 300).sum() >= 3 and ((lens >= 129) & (lens < 300)).sum() >= 1 and (lens < 129).sum() >= 3
+    fm = refload.load("envs.floor_map")
+    acts = ea.edge_schedule(110, 8, 32, scale=1.0, nonfinite=12)
+    run_lidar_env("rooms32_b8_edges", fm.FloorMapDatasetRooms(), False, 8, 8, 110, 12, acts)
+    acts = ea.edge_schedule(40, 4, 33, scale=1.5, nonfinite=0)
+    print("image_loc_edges", ea.assert_edges_hit(acts, nonfinite=False))
+    # pool seed 111: in none of its seven images do two of the eleven most unique grid positions tie (two positions
+    # that are each other's nearest neighbour tie exactly, and the reference's np.argsort orders ties as its
+    # unstable sort happens to; seeds 108-110 have such a tie)
+    run_image_env("loc_edges", "loc", (12, 12), 1, 3, (4, 4), 1.0, 9, False, 4, 40, 13, 7, 111, actions=acts)
+
+
 SECTIONS = {"rng": make_rng, "maps": make_maps, "loss": make_loss, "scan": make_lidar_scan,
             "lidar": make_lidar_env, "lidar_beams": make_lidar_env_beams, "image": make_image_env,
             "sparse": make_sparse_env, "circle_square": make_circle_square,
             "light_dark": make_light_dark, "render": make_render, "hf": make_hf, "pool": make_pool,
             "stream": make_stream, "scan_wide": make_scan_wide, "lidar_long": make_lidar_long,
-            "image_float": make_image_float_env}
+            "image_float": make_image_float_env, "edges": make_edges}
 
 
 def main(argv):

@@ -21,7 +21,8 @@ CE_RTOL = 0.0  # (bit-exact: numpy's float32 exp / log restated on the device)
 CE_ATOL = 0.0
 GOLDEN_CASES = ["cls_mnist", "cls_tin", "cls_gray3_rect", "loc_mnist", "loc_tin12", "loc_rect",
                 "cls_mnist_sparse", "loc_rect_sparse",  # *_sparse: the "-sparse" ids (SparsifyVectorWrapper)
-                "cls_f32rgb", "loc_f64gray3"]  # float32 RGB and float64 grey-as-RGB pools in [-0.2, 1.2]
+                "cls_f32rgb", "loc_f64gray3",  # float32 RGB and float64 grey-as-RGB pools in [-0.2, 1.2]
+                "loc_edges"]  # the edge-action schedule without its non-finite rows (tests/edge_actions.py)
 
 
 def _state_from_numpy(gen: np.random.Generator):
@@ -455,16 +456,18 @@ def _assert_stats_equal(got, want, n, where):
 
 
 def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0, dtype=np.uint8, obs_c=None, invert=False,
-                   log_stats=False, sparse=False, step_limit=16, pool_format=None):
+                   log_stats=False, sparse=False, step_limit=16, pool_format=None, actions=None, pool_len=300):
+    """actions: float32 [steps, n, 2] to step with instead of uniform(-1.5, 1.5) draws.  Returns the oracle-side
+    bool [steps] "this step moved the agents" (false on the batch autoreset steps, which ignore the action)."""
     import ap_gym_amd as ap
     from oracle import image_oracle as io
 
     rng = np.random.default_rng(n)
     if dtype == np.uint8:
-        pool = rng.integers(0, 256, (300, *shape), dtype=np.uint8)
+        pool = rng.integers(0, 256, (pool_len, *shape), dtype=np.uint8)
     else:
-        pool = rng.uniform(-0.2, 1.2, (300, *shape)).astype(dtype)
-    labels = rng.integers(0, k, 300)
+        pool = rng.uniform(-0.2, 1.2, (pool_len, *shape)).astype(dtype)
+    labels = rng.integers(0, k, pool_len)
     c = obs_c or (1 if len(shape) == 2 else shape[-1])
     ds = ap.ArrayImageClassificationDataset(pool, labels, k, c)
     cfg = ap.ImagePerceptionConfig(dataset=ds, sensor_size=sensor, sensor_scale=scale, step_limit=step_limit,
@@ -492,11 +495,16 @@ def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0, dtype=np.uint8, 
 
     saw(robs)
     arng = np.random.default_rng(3)
+    moved = []
     for t in range(steps):
         a = arng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+        if actions is not None:
+            a = actions[t]
         p = (arng.standard_normal((n, k)) if kind == "cls" else arng.uniform(-1, 1, (n, 2))).astype(np.float32)
+        moved.append(not ref.prev_done.any())
         got = env.step({"action": a, "prediction": p})
-        want = ref.step(a, p)
+        with np.errstate(over="ignore"):
+            want = ref.step(a, p)
         saw(want[0])
         assert set(got[0]) == set(want[0]), t
         for key in want[0]:
@@ -529,6 +537,34 @@ def _env_vs_oracle(kind, n, shape, sensor, k, steps, scale=1.0, dtype=np.uint8, 
         assert stats_steps >= 2
     if sparse and steps > step_limit:
         assert weights == {0.0, 1.0}
+    return np.array(moved)
+
+
+@pytest.mark.parametrize("case", [0, 8], ids=["loc-f32-1to1", "cls-u8-1to3"])
+def test_image_env_edge_actions_match_oracle(gpu, case):
+    """The edge-action schedule (tests/edge_actions.py) on two MATRIX_CASES shapes at n = 130, 40 steps: the first
+    test to reach move_pos with a norm of inf from overflowing squares (the move is [0, 0], base_reward -inf), a
+    norm one ulp either side of 1, signed zeros and moves too small to change the position.  The non-finite rows
+    are left out: a NaN glimpse position goes through scipy's float-to-int cast in the reference, which is
+    undefined, so the image envs' behaviour after a non-finite action is not pinned."""
+    import edge_actions as ea
+    from ap_gym_amd import _native as N
+
+    kind, shape, dtype, obs_c, sensor, scale, k, _, limit, invert, log_stats, sparse = MATRIX_CASES[case].values
+    n, steps = 130, 40
+    actions = ea.edge_schedule(steps, n, 61, scale=1.5, nonfinite=0)
+    moved = _env_vs_oracle(kind, n, shape, sensor, k, steps, scale, dtype=dtype, obs_c=obs_c, invert=invert,
+                           log_stats=log_stats, sparse=sparse, step_limit=limit, actions=actions,
+                           pool_format=N.APG_POOL_U8 if dtype == np.uint8 else N.APG_POOL_F32)
+    ea.assert_edges_hit(actions, np.broadcast_to(moved[:, None], (steps, n)), nonfinite=False)
+
+
+@pytest.mark.parametrize("kind,limit", [("cls", 129), ("cls", 300), ("loc", 129), ("loc", 300)])
+def test_image_env_long_episode_stats_match_oracle(gpu, kind, limit):
+    """Episodes of 129 and 300 steps with log_stats: the first image tests whose episode means go through
+    pw_sum_ptr's split levels (contiguous history; one and two levels deep).  n = 33, a pool of twelve 12 x 14
+    grey images, 2 L + 3 steps: two batch autoresets, every stats entry against the oracle's."""
+    _env_vs_oracle(kind, 33, (12, 14), (4, 4), 5, 2 * limit + 3, 1.5, log_stats=True, step_limit=limit, pool_len=12)
 
 
 def test_fused_step_largest_sensor_units_per_workgroup(gpu):

@@ -35,6 +35,8 @@ ENV_CASES = {
     "pool72_r60_b12": ("pool", 0, False, 12),
     "pool72_static_r9p5_b16": ("pool", 0, True, 16),
     "pool72_r28_b8_grid": ("pool", 0, False, 8),
+    # the edge-action schedule (tests/edge_actions.py): non-finite, overflowing, norm-1, zero and tiny actions
+    "rooms32_b8_edges": ("rooms", 32, False, 8),
 }
 POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index (make_lidar_long's too)
 
@@ -472,6 +474,57 @@ def test_long_range_matches_oracle(gpu, oracle_mod, kind, size, static, beams, l
     env.close()
 
 
+@pytest.mark.parametrize("kind,size,lidar_range,backend", [("rooms", 32, 5.0, "numpy"), ("rooms", 32, 5.0, "torch"),
+                                                           ("maze", 21, 5.0, "numpy"), ("rooms", 32, 8.0, "numpy")])
+def test_edge_actions_match_oracle(gpu, oracle_mod, kind, size, lidar_range, backend):
+    """The edge-action schedule (tests/edge_actions.py) at n = 300, 8 beams, at the default range (the resident
+    occupancy windows) and at range 8 (none).  The first test to reach phase 1 of k_lidar_step with `total` NaN (an
+    infinite action component: x / inf is NaN, `total > 0` is false and the agent stays, base_reward -inf), with
+    mag inf from overflowing squares (the move is [0, 0]: total 0), with mag one ulp either side of 1, and with
+    moves that vanish when added to the position (total 0 or one ulp of the position)."""
+    import torch
+
+    import ap_gym_amd as ap
+    import edge_actions as ea
+
+    n, steps, beams = 300, 110, 8
+    actions = ea.edge_schedule(steps, n, 51, scale=1.5, nonfinite=40)
+    preds = np.random.default_rng(52).uniform(-1, 1, (steps, n, 2)).astype(np.float32)
+    env = ap.LIDARLocalization2DVectorEnv(num_envs=n, dataset=_ds(ap, kind, size), lidar_beam_count=beams,
+                                          lidar_range=lidar_range, device=gpu, array_backend=backend)
+    ref = oracle_mod.OracleLidarVectorEnv(n, kind, size, False, 0, beams, lidar_range=lidar_range)
+    c = (lambda x: x.cpu().numpy()) if backend == "torch" else (lambda x: x)
+    obs, _ = env.reset(seed=17)
+    ref.reset(17)
+    assert np.array_equal(c(obs["lidar"]), ref.lidar)
+    stepped, terminated = [], []
+    for t in range(steps):
+        a, p = actions[t], preds[t]
+        if backend == "torch":
+            a, p = torch.from_numpy(a).to(gpu), torch.from_numpy(p).to(gpu)
+        obs, rew, term, trunc, info = env.step({"action": a, "prediction": p})
+        ref.step(actions[t], preds[t])
+        for key, want in (("lidar", ref.lidar), ("odometry", ref.odometry), ("time_step", ref.time_step)):
+            assert np.array_equal(c(obs[key]), want), (t, key)
+        assert np.array_equal(c(obs["map"])[..., 0], ref.map), t
+        assert np.array_equal(c(rew), ref.reward, equal_nan=True), t
+        assert np.array_equal(c(term), ref.terminated.astype(bool)), t
+        m = ref.info_mask.astype(bool)
+        assert np.array_equal(c(info["_base_reward"]) if "_base_reward" in info else np.zeros(n, bool), m), t
+        if m.any():
+            assert np.array_equal(c(info["base_reward"])[m], ref.base_reward[m]), t
+            assert np.array_equal(c(info["prediction"]["target"])[m], ref.target[m]), t
+            assert np.array_equal(c(info["prediction"]["loss"])[m], ref.loss[m]), t
+        stepped.append(m)
+        terminated.append(ref.terminated.astype(bool))
+    if backend == "torch":
+        env.check_errors()
+    env.close()
+    stepped, terminated = np.stack(stepped), np.stack(terminated)
+    ea.assert_edges_hit(actions, stepped)
+    assert ea.nonfinite_followups(actions, stepped, terminated) >= 3
+
+
 def _run_against_oracle(env, ref, seed, steps, action_seed):
     """reset(seed) and `steps` steps of env (numpy backend) against the oracle env: reset lidar and map, and per
     step lidar, odometry, time_step, reward, terminated and map.  Returns how often each env reset."""
@@ -607,9 +660,12 @@ def test_large_rooms_env_matches_oracle(gpu, oracle_mod, size, max_rooms, n):
     env.close()
 
 
-@pytest.mark.parametrize("step_limit,n,steps", [(1200, 64, 1210), (969, 32, 975)])
+@pytest.mark.parametrize("step_limit,n,steps", [(1200, 64, 1210), (969, 32, 975),
+                                                (129, 32, 141), (300, 32, 312), (968, 32, 980)])
 def test_long_episode_stats_match_oracle(gpu, oracle_mod, step_limit, n, steps):
-    """log_stats past 968 steps (the episode-end pairwise sums of k_episode_stats, seven split levels):
+    """log_stats past 968 steps (the episode-end pairwise sums of k_episode_stats, seven split levels) and at
+    129, 300 and 968 steps (the step kernel's own pw_sum_ptr, three split levels over the history at stride
+    num_envs: one, two and three levels deep; up to 128 steps the sum is a single leaf):
     the ActiveRegressionLogWrapper scalars of every episode end against numpy's means of the restated
     per-step metrics, the observations against the oracle env."""
     import ap_gym_amd as ap

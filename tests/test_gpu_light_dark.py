@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from test_oracle_golden import LIGHT_DARK_CASES, check_light_dark_step
+from test_oracle_golden import LIGHT_DARK_CASES, check_light_dark_step, light_dark_limit_of
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +60,8 @@ def test_light_dark_matches_reference_trace(gpu, name):
 
     g = golden(f"light_dark_{name}.npz")
     steps, n = g["actions"].shape[:2]
-    env = ap.make_vec("LightDark-sparse-v0" if LIGHT_DARK_CASES[name] else "LightDark-v0", num_envs=n)
+    env = ap.make_vec("LightDark-sparse-v0" if LIGHT_DARK_CASES[name] else "LightDark-v0", num_envs=n,
+                      max_episode_steps=light_dark_limit_of(g))
     obs, info = env.reset(seed=int(g["seed"]))
     # LightDarkEnv.reset returns {} (light_dark.py:121); the sparse fixture's reset keys are the
     # generation shim's (make_golden._reset_prediction_info_shim), not the reference's
@@ -81,7 +82,7 @@ def test_light_dark_matches_reference_trace(gpu, name):
                     assert all(type(x) is np.float32 for x in lst)
                     vec[key] += lst
     for key, v in vec.items():
-        assert np.array_equal(np.array(v, np.float32), g["stats_vector_" + key]), key
+        assert np.array_equal(np.array(v, np.float32), g["stats_vector_" + key], equal_nan=True), key
     env.close()
 
 
@@ -194,3 +195,201 @@ def test_light_dark_nan_errors(gpu):
     with pytest.raises(ValueError, match="NaN values detected in action."):
         tenv.step({"action": a, "prediction": np.zeros((4, 2), np.float32)})
     tenv.close()
+
+
+# ---------------------------------------------------------------------------- edge actions, long episodes, knobs
+LD_SCALES = (0.02, 0.05, 0.15, 0.4, 0.8, 1.5)  # per-env action scales: some episodes run to the limit, some leave early
+
+
+def _as_dict_torch(env, obs, rew, term, trunc, info):
+    """torch-mode step result -> the flat numpy form of _as_dict (stats of envs that did not finish: zeros)."""
+    c = lambda x: x.cpu().numpy()  # noqa: E731
+    pred = info["prediction"]
+    tgt = pred["target"]
+    out = {"noisy_position": c(obs["noisy_position"]), "time_step": c(obs["time_step"]), "reward": c(rew),
+           "terminated": c(term), "truncated": c(trunc), "info_mask": c(info["_base_reward"]),
+           "base_reward": c(info["base_reward"]), "loss": c(pred["loss"])}
+    if isinstance(tgt, dict):
+        out["weight"] = c(tgt["weight"])
+        tgt = tgt["target"]
+    out["target"] = c(tgt)
+    n = env.num_envs
+    out["stats_len"], out["stats"], out["stats_vectors"] = np.zeros(n, np.int32), np.zeros((4, n)), {}
+    if "stats" in info:
+        done = c(info["_stats"])
+        st = info["stats"]
+        out["stats_len"] = np.where(done, c(st["vector"]["length"]), 0).astype(np.int32)
+        for j, key in enumerate(env.STAT_NAMES):
+            out["stats"][j] = np.where(done, c(st["scalar"][key]).astype(np.float64), 0.0)
+        for i in np.nonzero(done)[0]:
+            k = out["stats_len"][i]
+            out["stats_vectors"][int(i)] = tuple(list(c(st["vector"][key][i, :k]))
+                                                 for key in ("euclidean_distance", "mse"))
+    return out
+
+
+def _numpy_stats_vectors(info):
+    out = {}
+    if "stats" in info:
+        for i in np.nonzero(info["_stats"])[0]:
+            out[int(i)] = tuple(info["stats"]["vector"][key][i] for key in ("euclidean_distance", "mse"))
+    return out
+
+
+def _follow_oracle(env, ref, seed, actions, preds, log_stats=True, env_ids=None):
+    """Reset both with `seed`, step both through the schedule and compare every output bit for bit (NaNs in the same
+    places).  Returns the oracle's per-step traces for the conditions a test puts on its own schedule."""
+    import torch
+
+    torch_mode = env.array_backend == "torch"
+    obs, _ = env.reset(seed=seed)
+    robs = ref.reset(seed, env_ids=env_ids)
+    got0 = obs["noisy_position"].cpu().numpy() if torch_mode else obs["noisy_position"]
+    assert np.array_equal(got0, robs["noisy_position"])
+    trace = {k: [] for k in ("info_mask", "terminated", "stats_len", "nan_obs")}
+    for t in range(len(actions)):
+        a, p = actions[t], preds[t]
+        if torch_mode:
+            res = env.step({"action": torch.as_tensor(a, device=env.device),
+                            "prediction": torch.as_tensor(p, device=env.device)})
+            got = _as_dict_torch(env, *res)
+        else:
+            res = env.step({"action": a, "prediction": p})
+            got = _as_dict(env, *res)
+            got["stats_vectors"] = _numpy_stats_vectors(res[4])
+        with np.errstate(invalid="ignore", over="ignore"):
+            want = ref.step(a, p)
+        for key in ("noisy_position", "time_step", "reward", "terminated", "truncated", "info_mask"):
+            assert np.array_equal(got[key], want[key], equal_nan=got[key].dtype.kind == "f"), (t, key)
+        m = want["info_mask"]
+        for key in ("base_reward", "loss"):
+            assert np.array_equal(np.where(m, got[key], 0), np.where(m, want[key], 0), equal_nan=True), (t, key)
+        assert np.array_equal(np.where(m[:, None], got["target"], 0), np.where(m[:, None], want["target"], 0),
+                              equal_nan=True), t
+        if ref.sparse:
+            assert np.array_equal(np.where(m, got["weight"], 0.0), want["weight"]), t
+        if log_stats:
+            assert np.array_equal(got["stats_len"], want["stats_len"]), t
+            done = want["stats_len"] > 0
+            assert np.array_equal(got["stats"][:, done], want["stats"][:, done], equal_nan=True), t
+            assert sorted(got["stats_vectors"]) == sorted(want["stats_vectors"]), t
+            for i, vecs in want["stats_vectors"].items():
+                for gv, wv in zip(got["stats_vectors"][i], vecs):
+                    assert all(type(x) is np.float32 for x in gv)
+                    assert np.array_equal(np.array(gv, np.float32), np.array(wv, np.float32), equal_nan=True), (t, i)
+        else:
+            assert "stats" not in res[4]
+        trace["info_mask"].append(m)
+        trace["terminated"].append(want["terminated"])
+        trace["stats_len"].append(want["stats_len"])
+        trace["nan_obs"].append(np.isnan(want["noisy_position"]).any(-1))
+    return {k: np.stack(v) for k, v in trace.items()}
+
+
+@pytest.mark.parametrize("backend", ["numpy", "torch"])
+@pytest.mark.parametrize("sparse", [False, True])
+def test_light_dark_edge_actions_match_oracle(gpu, backend, sparse):
+    """The edge-action schedule (tests/edge_actions.py) at n = 300: the first test to reach the kernel's clips with a
+    NaN (x / inf for an infinite action component: the position and both observation components are NaN until the
+    time limit, base_reward -inf, then target, loss, reward and the episode stats NaN), `mag > 1` with mag inf
+    (overflowing squares: the move is [0, 0]) and mag one ulp either side of 1."""
+    import ap_gym_amd as ap
+    import edge_actions as ea
+    from oracle.light_dark_oracle import LightDarkVectorOracle
+
+    n, steps = 300, 160
+    actions = ea.edge_schedule(steps, n, 41, scale=1.0, nonfinite=40)
+    preds = np.random.default_rng(42).uniform(-1, 1, (steps, n, 2)).astype(np.float32)
+    env = ap.LightDarkVectorEnv(n, log_stats=True, sparse=sparse, array_backend=backend)
+    tr = _follow_oracle(env, LightDarkVectorOracle(n, 50, sparse=sparse), 7, actions, preds)
+    env.close()
+    ea.assert_edges_hit(actions, tr["info_mask"])
+    assert ea.nonfinite_followups(actions, tr["info_mask"], tr["terminated"]) >= 3
+    assert tr["nan_obs"].sum() >= 100
+    # a NaN episode ended (at the time limit: a NaN position never leaves the square) and the env autoreset
+    assert (tr["nan_obs"][:-1] & tr["terminated"][:-1] & ~tr["info_mask"][1:]).sum() >= 3
+
+
+def _long_episode_inputs(n, steps, seed):
+    rng = np.random.default_rng(seed)
+    scales = np.resize(np.array(LD_SCALES), n)[None, :, None]
+    actions = (rng.uniform(-1, 1, (steps, n, 2)) * scales).astype(np.float32)
+    return actions, rng.uniform(-1, 1, (steps, n, 2)).astype(np.float32)
+
+
+# limit L: at least (episodes of 129 .. L-1 steps, of those not a multiple of 8, episodes of exactly L steps); the
+# oracle alone gives (0, 0, 34) at 129 (only the full length reaches the split), (13, 10, 26) at 300 and
+# (46, 38, 22) at 968
+LD_LONG_CASES = {129: (0, 0, 20), 300: (10, 8, 15), 968: (20, 10, 5)}
+
+
+@pytest.mark.parametrize("limit", sorted(LD_LONG_CASES))
+def test_light_dark_long_episode_stats_match_oracle(gpu, limit):
+    """Episodes of 129 .. 968 steps: the first LightDark test whose episode means go through pw_sum_ptr's split
+    levels (contiguous history); shorter episodes are one leaf.  24 envs with per-env action scales LD_SCALES,
+    2 L + 60 steps; all four stats scalars, stats_len and the vector lists against the oracle."""
+    import ap_gym_amd as ap
+    from oracle.light_dark_oracle import LightDarkVectorOracle
+
+    n, steps = 24, 2 * limit + 60
+    actions, preds = _long_episode_inputs(n, steps, 22)
+    env = ap.LightDarkVectorEnv(n, max_episode_steps=limit, log_stats=True)
+    tr = _follow_oracle(env, LightDarkVectorOracle(n, limit), 22, actions, preds)
+    env.close()
+    lens = tr["stats_len"][tr["stats_len"] > 0]
+    split = lens[(lens >= 129) & (lens < limit)]
+    counts = (len(split), int((split % 8 != 0).sum()), int((lens == limit).sum()))
+    print("light_dark long episodes", limit, counts)
+    assert all(c >= w for c, w in zip(counts, LD_LONG_CASES[limit])), counts
+
+
+def test_light_dark_limit_969_needs_log_stats_off(gpu):
+    """969 steps are one more than the in-kernel pairwise sum holds: refused with log_stats=True, fine without."""
+    import ap_gym_amd as ap
+    from oracle.light_dark_oracle import LightDarkVectorOracle
+
+    n = 16
+    actions, preds = _long_episode_inputs(n, 40, 23)
+    env = ap.LightDarkVectorEnv(n, max_episode_steps=969, log_stats=True)
+    with pytest.raises(ValueError, match="log_stats needs step_limit <= 968"):
+        env.reset(seed=1)
+    env.close()
+    env = ap.LightDarkVectorEnv(n, max_episode_steps=969, log_stats=False)
+    _follow_oracle(env, LightDarkVectorOracle(n, 969), 1, actions, preds, log_stats=False)
+    env.close()
+
+
+def test_light_dark_without_log_stats_matches_oracle(gpu):
+    import ap_gym_amd as ap
+    from oracle.light_dark_oracle import LightDarkVectorOracle
+
+    n, steps = 64, 120
+    actions, preds = _long_episode_inputs(n, steps, 24)
+    env = ap.LightDarkVectorEnv(n, log_stats=False)
+    tr = _follow_oracle(env, LightDarkVectorOracle(n, 50), 5, actions, preds, log_stats=False)
+    env.close()
+    assert (tr["stats_len"] == 50).sum() >= 10 and ((tr["stats_len"] > 0) & (tr["stats_len"] < 50)).sum() >= 10
+
+
+def test_light_dark_env_offset_is_a_slice_of_a_larger_env(gpu):
+    """env_offset=k: an env of m sub-envs equals rows k .. k+m of one larger env, step for step."""
+    import ap_gym_amd as ap
+
+    n, k, m, steps = 40, 13, 9, 120
+    actions, preds = _long_episode_inputs(n, steps, 25)
+    big = ap.LightDarkVectorEnv(n, log_stats=True)
+    part = ap.LightDarkVectorEnv(m, log_stats=True, env_offset=k)
+    ob, op = big.reset(seed=9)[0], part.reset(seed=9)[0]
+    for key in ob:
+        assert np.array_equal(ob[key][k:k + m], op[key]), key
+    episodes = 0
+    for t in range(steps):
+        gb = _as_dict(big, *big.step({"action": actions[t], "prediction": preds[t]}))
+        gp = _as_dict(part, *part.step({"action": actions[t, k:k + m], "prediction": preds[t, k:k + m]}))
+        for key, v in gp.items():
+            want = gb[key][:, k:k + m] if key == "stats" else gb[key][k:k + m]
+            assert np.array_equal(v, want), (t, key)
+        episodes += int((gp["stats_len"] > 0).sum())
+    assert episodes >= 2 * m
+    big.close()
+    part.close()

@@ -39,6 +39,8 @@ ENV_CASES = {
     "pool72_r60_b12": ("pool", 0, False, 12),
     "pool72_static_r9p5_b16": ("pool", 0, True, 16),
     "pool72_r28_b8_grid": ("pool", 0, False, 8),
+    # the edge-action schedule (tests/edge_actions.py): non-finite, overflowing, norm-1, zero and tiny actions
+    "rooms32_b8_edges": ("rooms", 32, False, 8),
 }
 POOL_STATIC_INDEX = 5  # make_golden.make_pool's static_map_index (make_lidar_long's too)
 
@@ -188,7 +190,8 @@ def test_vector_env_trace(oracle_mod, name):
 
 IMAGE_CASES = ["cls_mnist", "cls_tin", "cls_gray3_rect", "loc_mnist", "loc_tin12", "loc_rect",
                "cls_mnist_sparse", "loc_rect_sparse",  # *_sparse: SparsifyVectorWrapper over the log wrapper
-               "cls_f32rgb", "loc_f64gray3"]  # float pools in [-0.2, 1.2]: cast to float32, not divided by 255
+               "cls_f32rgb", "loc_f64gray3",  # float pools in [-0.2, 1.2]: cast to float32, not divided by 255
+               "loc_edges"]  # the edge-action schedule without its non-finite rows (tests/edge_actions.py)
 
 
 @pytest.mark.parametrize("name", IMAGE_CASES)
@@ -293,7 +296,14 @@ def test_hide_and_seek_oracle_matches_reference_autoreset_steps():
 
 
 # ---------------------------------------------------------------------------- LightDark
-LIGHT_DARK_CASES = {"n8": False, "n6_wide": False, "n5_sparse": True}
+LIGHT_DARK_CASES = {"n8": False, "n6_wide": False, "n5_sparse": True,
+                    # the edge-action schedule (tests/edge_actions.py); episodes up to a time limit of 300
+                    "edges": False, "limit300": False}
+
+
+def light_dark_limit_of(g) -> int:
+    """The TimeLimit a trace was recorded at (fixtures without the entry: the registered 50)."""
+    return int(g["max_episode_steps"]) if "max_episode_steps" in g.files else 50
 
 
 def check_light_dark_step(g, t, got, rtol=0.0):
@@ -303,13 +313,14 @@ def check_light_dark_step(g, t, got, rtol=0.0):
     m = g["step_info_mask"][t]
     for key in ("base_reward", "loss"):
         assert np.array_equal(np.where(m, got[key], 0), g["step_" + key][t], equal_nan=True), (t, key)
-    assert np.array_equal(np.where(m[:, None], got["target"], 0), g["step_target"][t]), t
+    assert np.array_equal(np.where(m[:, None], got["target"], 0), g["step_target"][t], equal_nan=True), t
     if "step_weight" in g.files:
         assert np.array_equal(np.where(m, got["weight"], 0.0), g["step_weight"][t]), t
     assert np.array_equal(got["stats_len"], g["step_stats_len"][t]), t
     names = ("avg_euclidean_distance", "avg_mse", "final_euclidean_distance", "final_mse")
     for j, key in enumerate(names):
-        assert np.array_equal(np.where(got["stats_len"] > 0, got["stats"][j], 0.0), g["step_stats_" + key][t]), (t, key)
+        assert np.array_equal(np.where(got["stats_len"] > 0, got["stats"][j], 0.0), g["step_stats_" + key][t],
+                              equal_nan=True), (t, key)
 
 
 @pytest.mark.parametrize("name", sorted(LIGHT_DARK_CASES))
@@ -318,17 +329,41 @@ def test_light_dark_oracle_matches_reference_trace(name):
 
     g = golden(f"light_dark_{name}.npz")
     steps, n = g["actions"].shape[:2]
-    ref = LightDarkVectorOracle(n, 50, sparse=LIGHT_DARK_CASES[name])
+    ref = LightDarkVectorOracle(n, light_dark_limit_of(g), sparse=LIGHT_DARK_CASES[name])
     obs = ref.reset(int(g["seed"]))
     assert np.array_equal(obs["noisy_position"], g["reset_noisy_position"])
     assert np.array_equal(obs["time_step"], g["reset_time_step"])
     vec = {"euclidean_distance": [], "mse": []}
     for t in range(steps):
-        out = ref.step(g["actions"][t], g["predictions"][t])
+        with np.errstate(invalid="ignore", over="ignore"):
+            out = ref.step(g["actions"][t], g["predictions"][t])
         check_light_dark_step(g, t, out)
         for i in sorted(out["stats_vectors"]):
             ed, ms = out["stats_vectors"][i]
             vec["euclidean_distance"] += ed
             vec["mse"] += ms
     for key, v in vec.items():
-        assert np.array_equal(np.array(v, np.float32), g["stats_vector_" + key]), key
+        assert np.array_equal(np.array(v, np.float32), g["stats_vector_" + key], equal_nan=True), key
+
+
+def test_edge_fixtures_hold_every_class():
+    """The edge fixtures' schedules hit every class of the table at least 10 times on stepped envs; the LightDark
+    one also holds NaN observations, at least 3 envs that go on for 5 steps after a non-finite action, a NaN
+    episode that runs to the time limit and autoresets, and NaN episode statistics."""
+    import edge_actions as ea
+
+    g = golden("light_dark_edges.npz")
+    stepped, term = g["step_info_mask"], g["step_terminated"]
+    ea.assert_edges_hit(g["actions"], stepped)
+    assert ea.nonfinite_followups(g["actions"], stepped, term) >= 3
+    nanpos = np.isnan(g["step_noisy_position"]).any(-1)
+    assert (nanpos[:-1] & term[:-1] & ~stepped[1:]).any()
+    assert np.isnan(g["step_target"]).any() and np.isnan(g["step_stats_avg_mse"]).any()
+    d = golden("lidar_env_rooms32_b8_edges.npz")
+    ea.assert_edges_hit(d["actions"], d["info_mask"])
+    assert ea.nonfinite_followups(d["actions"], d["info_mask"], d["terminated"]) >= 3
+    g = golden("image_loc_edges.npz")
+    moved = ~np.concatenate([[False], g["step_terminated"][:-1, 0]])  # the batch autoreset steps ignore the action
+    ea.assert_edges_hit(g["actions"], np.broadcast_to(moved[:, None], g["actions"].shape[:2]), nonfinite=False)
+    lens = golden("light_dark_limit300.npz")["step_stats_len"]
+    assert (lens == 300).sum() >= 3 and ((lens >= 129) & (lens < 300)).sum() >= 1
